@@ -11,11 +11,14 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   starts them itself (``launch_ranks``: re-executes itself under torch.distributed.run on 127.0.0.1 and a free port,
   passes the ranks' output through and returns their exit code; the reference's counterpart is
   ``python -m torch.distributed.launch --nproc_per_node=N``, SRGAN/train_S1.sh:1-8).
-Prints ONE JSON line on rank 0 with the metric, ``roofline`` (dominant scan kernel: algorithmic
-bytes / HIP-event kernel time, measured inside the timed region by the library's own events) and
-``cpu_baseline`` (the same training step on the host cores with the CPU oracle as the scan, N = 1
-only, one batch-1 step; plus BASELINE.json configs[0] -- ONE OSS block on (2,48,48,48), forward and
-forward+backward, median of 3 -- as SURVEY.md section 8d defines it).  Synthetic data, random-init weights.
+Prints ONE JSON line on rank 0 with the metric (``value``, ``ms_per_step`` of the ``--steps K`` timed steps).  A plain run
+does only that: set-up, W warm-up steps, K timed steps, the line.  ``--full`` adds what needs runs of its own:
+``roofline`` (dominant scan kernel: algorithmic bytes / HIP-event kernel time, measured by the library's own events;
+``non_scan``: a kernel-traced run of this script), ``cpu_baseline`` (the same training step on the host cores with the CPU
+oracle as the scan, N = 1 only, one batch-1 step; plus BASELINE.json configs[0] -- ONE OSS block on (2,48,48,48), forward and
+forward+backward, median of 3 -- as SURVEY.md section 8d defines it) and ``secondary`` (the other precision and workloads
+below, each in a process of its own); without ``--full`` these three are null.  Synthetic data, random-init weights.
+``--dump-outputs DIR``: what the last timed step computed, as DIR/<name>.npy in float32 (``dump_outputs``).
 
 Other workloads of BASELINE.json (not the driver's default line):
   --global-batch 32      configs[2]: fixed global batch split over the ranks (32/16/8/4 per GPU), "scaling": "strong"
@@ -54,11 +57,61 @@ NET_REALSR = dict(type="MambaRealSR11", inp_channels=3, out_channels=3, scale=4,
                   num_refinement_blocks=6, heads=[1, 2, 4, 8], ffn_expansion_factor=2.66, bias=False,
                   LayerNorm_type="WithBias")
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.29 TB/s measured copy)
+DUMP_CAP = 4 << 20      # elements per dumped array (16 MB of float32); a larger output is written as a fixed sample
 _T0 = time.time()
 
 
 def log(msg):
     print(f"[bench +{time.time() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(d, arrays):
+    """``--dump-outputs DIR``: ``arrays`` (name -> tensor) as DIR/<name>.npy in float32, so that two builds can be compared
+    output for output.  An array of more than DUMP_CAP elements is flattened and sampled: DUMP_CAP indices drawn without
+    replacement by a generator seeded with 0, in increasing order -- the same elements in every run of the same arguments.  The
+    training step itself is not bit-reproducible from run to run, so two dumps are compared with a tolerance."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_CAP, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log(f"outputs of the last timed step written to {d}: {', '.join(sorted(arrays))}")
+
+
+#: the vendor library's solver search (--miopen-find 1) as recorded for the headline step (configs[1], bf16, batch 8) on an MI355X:
+#: MIOpen's user find database (solver timings per convolution problem) and user perf database (the tuned parameters of the winners),
+#: under the names MIOpen itself gives them (GPU, CU count, library version).  Re-recorded by a run with MIOPEN_USER_DB_PATH set to an
+#: empty directory, whose two *.txt files are copied here.  Files of another GPU or library version are never read by MIOpen.
+SOLVER_DB = os.path.join(ROOT, "bench_data", "miopen")
+
+
+def seed_solver_db():
+    """``--miopen-find 1`` without a user database of the caller's (MIOPEN_USER_DB_PATH): a per-run copy of SOLVER_DB becomes the
+    user database, so that the convolutions recorded there start from their recorded search instead of searching again (37 s of
+    start-up on a fresh home directory); a convolution that is not recorded is searched as before.  -> the directory, or None."""
+    import atexit
+    import shutil
+    import tempfile
+    if "MIOPEN_USER_DB_PATH" in os.environ or not os.path.isdir(SOLVER_DB):
+        return None
+    d = tempfile.mkdtemp(prefix="bench-miopen-db-")
+    for f in os.listdir(SOLVER_DB):
+        shutil.copy(os.path.join(SOLVER_DB, f), d)
+    os.environ["MIOPEN_USER_DB_PATH"] = d
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    return d
+
+
+def train_outputs(loss, params, ema):
+    """what a caller of the training step receives: the loss of the step and the trained state it leaves (every trainable
+    parameter, flattened and concatenated in ``named_parameters`` order; the EMA weights in the same order where there are any)"""
+    out = {"loss": loss.detach().reshape(1), "params": torch.cat([p.detach().reshape(-1) for p in params])}
+    if ema is not None:
+        out["ema"] = torch.cat([e.detach().reshape(-1) for e in ema])
+    return out
 
 
 def usable_cores() -> int:
@@ -113,8 +166,8 @@ def make_eager(model, net, ema, derain, acdt):
 
 def bench_realsr_tiled(args):
     """BASELINE.json configs[4]: RealSR inference 512x512 -> 2048x2048, tiled (RealESRGANer rule: tile 128 + halo 16), fp16, one
-    hipGraph per padded-tile shape.  One "step" = one image.  Single GPU.  Also timed: tile 256 + halo 16 and the reference's
-    default tile = 0 (untiled), each with its own scan roofline.  pre_pad 0: the 3-level UNet needs every window to
+    hipGraph per padded-tile shape.  One "step" = one image.  Single GPU.  Also timed with ``--full``: tile 256 + halo 16 and the
+    reference's default tile = 0 (untiled), and each tiling's scan roofline.  pre_pad 0: the 3-level UNet needs every window to
     be a multiple of 8 pixels (PixelUnshuffle), and 512 + the script's default pre-pad of 10 leaves a 10-pixel last column
     of cells -- the reference net raises on it just the same."""
     if not torch.cuda.is_available():
@@ -137,7 +190,7 @@ def bench_realsr_tiled(args):
     torch.manual_seed(0)
     net = build_network(NET_REALSR).to(dev)
     img = torch.rand(1, 3, 512, 512, device=dev)
-    res = {}
+    res, outs = {}, {}
     ref = None
     # (round 5) tile 256: the reference's tile size is a free argument (RealSR/VmambaIR/utils.py:33, default 0 = the whole image in one
     # forward); 512 x 512 in tiles of 256 + halo 16 is FOUR tiles of ONE padded shape (272 x 272) = one stacked forward per image
@@ -149,7 +202,7 @@ def bench_realsr_tiled(args):
                                         ("graph_4_tiles_stacked_shapes_side_by_side", True, 4, True, 128),
                                         ("tile256_eager", False, 1, False, 256), ("tile256_graph_4_tiles_stacked", True, 4, False, 256),
                                         ("untiled_eager", False, 1, False, 0), ("untiled_graph", True, 1, False, 0)):
-        if only_legs and name not in only_legs:
+        if (only_legs and name not in only_legs) or (not only_legs and tile != 128 and not args.full):
             continue
         drv = RealSREnhancer(net, 4, tile=tile, tile_pad=16, pre_pad=0, half=True, use_graph=graph, batch_tiles=bt, concurrent_shapes=conc)
         runs = (lambda d=drv: d.tiled.tiles_run) if tile else (lambda d=drv: d.whole.calls)
@@ -178,9 +231,14 @@ def bench_realsr_tiled(args):
                      "tiles_per_image": tiles, "graphs": drv.tiled.n_graphs if tile else drv.whole.n_graphs, "tiles_per_forward": bt,
                      "shapes_side_by_side": conc, "tile": tile, "tile_pad": 16 if tile else 0,
                      "max_abs_diff_vs_eager": float((out.float() - ref).abs().max())}
+        if args.dump_outputs:
+            outs[name] = out.float().cpu()
         del drv
         torch.cuda.empty_cache()
 
+    if args.dump_outputs:   # the output of the leg `value` reports (with VMAMBAIR_REALSR_LEGS: of the fastest leg timed)
+        pick = [k for k in res if res[k]["tile"] == 128 and not only_legs] or list(res)
+        dump_outputs(args.dump_outputs, {"output": outs[max(pick, key=lambda k: res[k]["images_per_s"])]})
     if only_legs:
         print(json.dumps({"legs": res}), flush=True)
         return
@@ -214,26 +272,28 @@ def bench_realsr_tiled(args):
                 "measured": "HIP events around every scan launch of one eager pass over the same tiles, one tile at a time"}
 
     # padded tile of the baseline tiling: 128 + 2 x 16 = 160 x 160 interior tiles; tile 256: 272 x 272; untiled: 512 x 512
-    roof = scan_roofline(128, "u:(1,96,25600)")
-    roof256 = scan_roofline(256, "u:(1,96,73984)")
-    roof0 = scan_roofline(0, "u:(1,96,262144)")
     base = {k: v for k, v in res.items() if v["tile"] == 128}
     g = max(base.values(), key=lambda r: r["images_per_s"])
-    best256 = max((v for v in res.values() if v["tile"] == 256), key=lambda r: r["images_per_s"])
-    best0 = max((v for v in res.values() if v["tile"] == 0), key=lambda r: r["images_per_s"])
-    other = {"tile_256_plus_halo_16": {"images_per_s": best256["images_per_s"], "s_per_image": best256["s_per_image"],
-                                       "note": "four tiles of ONE padded shape (272 x 272) = one stacked forward per image; a different approximation "
-                                               "of the image than tile 128 (the channel branch pools per tile)", "roofline": roof256},
-             "untiled_tile_0_reference_default": {"images_per_s": best0["images_per_s"], "s_per_image": best0["s_per_image"],
-                                                   "note": "RealESRGANer's default tile = 0 (utils.py:32): the whole image in one forward, L = 262144",
-                                                   "roofline": roof0}}
+    roof = other = None
+    if args.full:
+        roof = scan_roofline(128, "u:(1,96,25600)")
+        roof256 = scan_roofline(256, "u:(1,96,73984)")
+        roof0 = scan_roofline(0, "u:(1,96,262144)")
+        best256 = max((v for v in res.values() if v["tile"] == 256), key=lambda r: r["images_per_s"])
+        best0 = max((v for v in res.values() if v["tile"] == 0), key=lambda r: r["images_per_s"])
+        other = {"tile_256_plus_halo_16": {"images_per_s": best256["images_per_s"], "s_per_image": best256["s_per_image"],
+                                           "note": "four tiles of ONE padded shape (272 x 272) = one stacked forward per image; a different "
+                                                   "approximation of the image than tile 128 (the channel branch pools per tile)", "roofline": roof256},
+                 "untiled_tile_0_reference_default": {"images_per_s": best0["images_per_s"], "s_per_image": best0["s_per_image"],
+                                                       "note": "RealESRGANer's default tile = 0 (utils.py:32): the whole image in one forward, "
+                                                               "L = 262144", "roofline": roof0}}
     print(json.dumps({
         "metric": "images/sec, x4 real-world SR inference 512x512 -> 2048x2048, tiled, fp16", "value": g["images_per_s"],
         "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(g["s_per_image"] * 1e3, 2),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
         "config": {"workload": "BASELINE.json configs[4]: MambaRealSR11 [6,2,2,1]+6 dim48, fp16 autocast (scan arithmetic f32), "
                                "no_grad, 512x512 LQ, RealESRGANer rule tile 128 + halo 16, pre_pad 0 (`value` = the fastest leg of THIS tiling, "
-                               "the one rounds 2-4 and BASELINE.md quote; tile 256 and the untiled default are in `other_tilings`)",
+                               "the one rounds 2-4 and BASELINE.md quote; with --full, tile 256 and the untiled default are in `other_tilings`)",
                    "tiles_per_image": g["tiles_per_image"], "tiles_per_s": g["tiles_per_s"], "hipgraphs": g["graphs"],
                    "tiles_per_forward": g["tiles_per_forward"], "other_tilings": other, **res},
         "roofline": roof, "cpu_baseline": None}), flush=True)
@@ -251,7 +311,7 @@ def bench_srgan_split64(args):
     torch.manual_seed(0)
     net = build_network(NET).to(dev)
     lq = torch.rand(1, 3, 256, 256, device=dev)
-    res, ref = {}, None
+    res, outs, ref = {}, {}, None
     for name, graph, bt in (("eager_cell_by_cell", False, 1), ("graph_cell_by_cell", True, 1), ("graph_16_cells_stacked", True, 16)):
         drv = Split64SR(net, 4, autocast_dtype=torch.bfloat16, use_graph=graph, batch_tiles=bt)
         out = drv(lq)
@@ -268,7 +328,11 @@ def bench_srgan_split64(args):
             ref = out.clone()
         res[name] = {"s_per_image": round(dt, 4), "images_per_s": round(1.0 / dt, 3), "cells_per_s": round(16 / dt, 1),
                      "forwards_per_image": 16 // bt, "max_abs_diff_vs_eager": float((out - ref).abs().max())}
+        if args.dump_outputs:
+            outs[name] = out.float().cpu()
     best = max(res.values(), key=lambda r: r["images_per_s"])
+    if args.dump_outputs:   # the output of the leg `value` reports
+        dump_outputs(args.dump_outputs, {"output": outs[max(res, key=lambda k: res[k]["images_per_s"])]})
     print(json.dumps({
         "metric": "images/sec, x4 SR validation inference in 64x64 cells (MambaSISRModel2.test), 256x256 LQ", "value": best["images_per_s"],
         "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(best["s_per_image"] * 1e3, 2),
@@ -568,7 +632,7 @@ def secondary_workloads():
                         ("realsr_tiled", ["--config", "realsr-tiled", "--steps", "2", "--warmup", "1"])):
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, me, *extra, "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True,
+            r = subprocess.run([sys.executable, me, *extra, "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True,
                                timeout=240)
             j = json.loads(r.stdout.strip().splitlines()[-1])
             roof = j.get("roofline") or {}
@@ -667,25 +731,33 @@ def main():
                     help="fixed GLOBAL batch split over the ranks (BASELINE.json configs[2]: 32 -> 32/16/8/4 per GPU); scaling = strong")
     ap.add_argument("--config", choices=["sr", "deraining", "realsr-tiled", "srgan-split64"], default="sr")
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own, after the timed steps: `roofline` (scan kernels timed by the library's "
+                         "events, HBM copy kernel, the kernel-traced `non_scan` run, SQ counters), `cpu_baseline` and the `secondary` "
+                         "workloads; without it these are null and the run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 16 MB per array: a seeded "
+                         "sample of anything larger); the inputs are the same in every run of the same arguments")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the trailing Deraining / RealSR legs of the default single-GPU run (the `secondary` block)")
+                    help="--full: skip the trailing Deraining / RealSR legs of the single-GPU run (the `secondary` block)")
     ap.add_argument("--micro-streams", type=int, default=int(os.environ.get("VMAMBAIR_MICRO_STREAMS", "1")),
                     help="micro-batches of the per-GPU batch run as parallel branches of the step's graph (train_graph.py)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("VMAMBAIR_BENCH_GRAPH", "1")),
                     help="1: replay the training step as one hipGraph (single GPU, or manual flat-gradient "
                          "all-reduce outside the graph for N > 1)")
     ap.add_argument("--skip-roofline", action="store_true",
-                    help="graph mode: do not run the trailing eager steps that time the scan kernels (profiling runs)")
+                    help="--full, graph mode: do not run the trailing eager steps that time the scan kernels (profiling runs)")
     ap.add_argument("--miopen-find", type=int, default=None,
                     help="1: torch.backends.cudnn.benchmark = True, as the reference's training pipelines set it "
                          "(SRGAN/VmambaIR/train_pipeline.py:97, Deraining/basicsr/train.py:135) -- the vendor library searches its solvers "
                          "for the UNet skeleton's GEMM-shaped 3x3 convolutions during the warm-up (before the capture) instead of taking "
                          "its heuristic's pick: 228.1 -> 232.0 images/s, 37 s more start-up (profiles/r04_multirank_flow_check_and_"
-                         "miopen_find.txt).  Default: 1 for the 16-bit training workloads, 0 for --dtype fp32 (3 minutes of search for "
-                         "+0.3 %) and for the inference configs; VMAMBAIR_MIOPEN_FIND overrides the default")
+                         "miopen_find.txt) -- unless the search of that convolution is recorded under bench_data/miopen/ (seed_solver_db: "
+                         "the headline step's are).  Default: 1 for the 16-bit training workloads, 0 for --dtype fp32 (3 minutes of search for "
+                         "+0.3 %%) and for the inference configs; VMAMBAIR_MIOPEN_FIND overrides the default")
     ap.add_argument("--no-non-scan", action="store_true",
-                    help="skip `roofline.non_scan` (a second, kernel-traced run of this script: rocprofv3 --kernel-trace, about 40 s)")
+                    help="--full: skip `roofline.non_scan` (a second, kernel-traced run of this script: rocprofv3 --kernel-trace, about 40 s)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--share-gpu", action="store_true",
@@ -718,6 +790,7 @@ def main():
         return rendezvous_only(world, rank)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the HIP scan has no CPU path)")
+    solver_db = seed_solver_db() if args.miopen_find else None
     if args.share_gpu:
         local_rank = local_rank % max(1, torch.cuda.device_count())
     if torch.cuda.device_count() < (1 if args.share_gpu else max(world, local_rank + 1)):
@@ -824,7 +897,8 @@ def main():
                                     overlap_wgrads=os.environ.get("VMAMBAIR_OVERLAP_WGRADS", "0") == "1", grad_buckets=nb,
                                     allreduce_via_host=via_host, **opt_kw)
         log("capturing the training step")
-        lib.oss_prof_family_enable(1)     # algorithmic bytes per non-scan kernel family, per pass (warm-up passes + the captured one)
+        # --full: algorithmic bytes per non-scan kernel family, per pass (warm-up passes + the captured one), for `roofline.non_scan`
+        lib.oss_prof_family_enable(1 if args.full else 0)
         try:
             step = make_step(buckets)
             step.capture(lq, gt)
@@ -839,11 +913,11 @@ def main():
             from vmambair_amd.ops import _common as _oc
             _oc._DEFER_KEEP = _oc._DEFER_OUTS = _oc._WGRAD_OPERANDS = _oc._WGRAD_STORAGES = _oc._WGRAD_FLUSHER = None
             torch.cuda.synchronize()
-            lib.oss_prof_family_enable(1)
+            lib.oss_prof_family_enable(1 if args.full else 0)
             step = make_step(1)
             step.capture(lq, gt)
         lib.oss_prof_family_enable(0)
-        fam_counts = family_counts(lib, step.warmup + 1)
+        fam_counts = family_counts(lib, step.warmup + 1) if args.full else None
         log("captured")
     else:
         ema = [p.detach().clone() for p in net.parameters()]
@@ -862,7 +936,7 @@ def main():
     if args.graph and world > 1:
         step.time_allreduce()
     lib.oss_prof_reset()
-    lib.oss_prof_enable(0 if args.graph else 1)
+    lib.oss_prof_enable(1 if (args.full and not args.graph) else 0)   # --full, eager steps: the roofline's events in the timed region
     st_ = torch.cuda.current_stream().cuda_stream
     lib.oss_prof_marker(1, st_)   # kernel-trace markers around the timed region (tools/prof_summary.py), outside the clock
     fence()
@@ -875,13 +949,16 @@ def main():
     lib.oss_prof_enable(0)
     log(f"timed {args.steps} steps in {dt:.3f}s")
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:   # before anything below runs the net again
+        dump_outputs(args.dump_outputs, train_outputs(loss, step.params if args.graph else list(net.parameters()),
+                                                      step.ema if args.graph else (None if derain else ema)))
     # peak device memory of the captured step (graph pool included) and what the deferred weight gradients held (ADVICE r3:
     # recorded products keep both operands alive until the grouped launch; bounded by VMAMBAIR_WGRAD_KEEP_MB, ops/_common.py)
     peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 1e9, 3)
     wgrad_stats = getattr(step, "wgrad_stats", None) if args.graph else None
     allreduce_ms = step.collect_allreduce_ms() if (args.graph and world > 1) else None
     prof_note = "HIP events around every scan kernel launch inside the timed region"
-    if args.graph and args.skip_roofline:
+    if args.graph and (args.skip_roofline or not args.full):
         prof_steps = 1
     elif args.graph:
         # kernels inside a replayed graph cannot be bracketed by host-recorded events: time the very
@@ -951,23 +1028,23 @@ def main():
                          "alg_GBps": round(r["alg_bytes"] / (r["total_ms"] * 1e-3) / 1e9, 1)} for r in recs],
                     "scan_ms_per_step": round(sum(r["total_ms"] for r in recs) / prof_steps, 3),
                     "measured": prof_note}
-        # achievable HBM bandwidth, same run (copy kernel, 1 GiB)
-        n = 1 << 30
-        src = torch.empty(n, dtype=torch.uint8, device=dev).fill_(1)
-        dst = torch.empty_like(src)
-        st = torch.cuda.current_stream().cuda_stream
-        lib.oss_hbm_copy(src.data_ptr(), dst.data_ptr(), n, st)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
+        if args.full:   # achievable HBM bandwidth, same run (copy kernel, 1 GiB)
+            n = 1 << 30
+            src = torch.empty(n, dtype=torch.uint8, device=dev).fill_(1)
+            dst = torch.empty_like(src)
+            st = torch.cuda.current_stream().cuda_stream
             lib.oss_hbm_copy(src.data_ptr(), dst.data_ptr(), n, st)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbps = 5 * 2 * n / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        if roof is not None:
-            roof["copy_kernel_GBps"] = round(copy_gbps, 1)
-        del src, dst
-        if roof is not None and args.graph and world == 1 and not args.no_non_scan and not args.skip_roofline:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                lib.oss_hbm_copy(src.data_ptr(), dst.data_ptr(), n, st)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbps = 5 * 2 * n / (e0.elapsed_time(e1) * 1e-3) / 1e9
+            if roof is not None:
+                roof["copy_kernel_GBps"] = round(copy_gbps, 1)
+            del src, dst
+        if roof is not None and args.full and args.graph and world == 1 and not args.no_non_scan and not args.skip_roofline:
             log("non-scan roofline: kernel trace of the same step (rocprofv3 subprocess)")
             torch.cuda.empty_cache()
             targv = ["--config", args.config, "--dtype", args.dtype, "--batch-per-gpu", str(B), "--patch", str(args.patch), "--miopen-find", "0",
@@ -978,7 +1055,7 @@ def main():
                 roof["valu_busy_measured"] = measure_valu_busy(f"{B},96,4096", "bf16" if args.dtype == "bf16" else "f32")
 
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline (subprocess, 300 s limit)")
             import subprocess
             try:  # own process: no GPU context, own thread pools, bounded time
@@ -989,7 +1066,7 @@ def main():
                 cpu = {"error": str(e)[:200]}
 
         second = None
-        if world == 1 and args.config == "sr" and not args.global_batch and not args.no_secondary:
+        if args.full and world == 1 and args.config == "sr" and not args.global_batch and not args.no_secondary:
             log("secondary workloads (configs[3], configs[4]; subprocesses, 240 s limit each)")
             second = secondary_workloads()
 
@@ -1010,6 +1087,9 @@ def main():
                        "global_batch": world * B, "per_gpu_batch": B, "lq": list(lq.shape[-2:]), "gt": list(gt.shape[-2:]),
                        "parallelism": f"dp{world}", "step_launch": "hipGraph replay" if args.graph else "eager",
                        "vendor_conv_solver_search": bool(args.miopen_find),
+                       # where the search started from: the recorded results of bench_data/miopen/ (seed_solver_db) or the caller's own
+                       # user database / none
+                       "vendor_conv_solver_records": "bench_data/miopen" if solver_db else None,
                        "optimizer": ("AdamW 3e-4 (0.9,0.999) decay 1e-4 + clip_grad_norm 0.01, no EMA" if derain else
                                      "Adam 2e-4 (0.9,0.99) + EMA 0.999"), "loss": "L1",
                        # multi-GPU exchange: ONE flat fp32 all-reduce between the forward+backward graph and the optimizer graph

@@ -531,6 +531,52 @@ def test_bench_non_scan_roofline_table_from_counts_and_a_trace():
     assert all("marker" not in k["kernel"] for k in r["top_kernels"])
 
 
+def test_bench_dump_outputs_float32_and_the_same_sample_every_run(tmp_path):
+    """bench.py ``--dump-outputs``: loss, flattened parameters and EMA weights as float32 .npy files; an array above DUMP_CAP
+    elements becomes a sample of DUMP_CAP elements that is the same in every run (two builds compare output for output)"""
+    import importlib.util
+    import os
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_CAP = 1000
+    params = [torch.arange(600, dtype=torch.float32).reshape(20, 30), torch.arange(600, 1200, dtype=torch.float64)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), bench.train_outputs(torch.tensor(0.25, dtype=torch.bfloat16), params, params[:1]))
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["ema.npy", "loss.npy", "params.npy"] and all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].tolist() == [0.25]
+    assert a["ema.npy"].tolist() == list(range(600))                  # under the cap: whole, in parameter order
+    p = a["params.npy"]
+    assert p.shape == (1000,) and len(set(p.tolist())) == 1000 and np.all(np.diff(p) > 0) and p.max() < 1200   # sampled, in order
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f)) for f, v in a.items())
+    assert set(bench.train_outputs(torch.tensor(1.0), params, None)) == {"loss", "params"}
+
+
+def test_bench_solver_db_seeds_a_per_run_copy_unless_the_caller_has_one(monkeypatch):
+    """bench.py ``seed_solver_db``: the recorded vendor solver search (bench_data/miopen/: MIOpen's user find and perf databases,
+    one line per convolution problem) is copied into a fresh directory that becomes MIOPEN_USER_DB_PATH -- the committed files are
+    never the database MIOpen writes to -- and a database the caller named is left alone"""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    recorded = sorted(os.listdir(bench.SOLVER_DB))
+    assert [f.rsplit(".", 2)[1:] for f in recorded] == [["udb", "txt"], ["ufdb", "txt"]]
+    lines = [open(os.path.join(bench.SOLVER_DB, f)).read().splitlines() for f in recorded]
+    assert len(lines[0]) == len(lines[1]) > 0 and all("=" in ln for ln in lines[0] + lines[1])
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", "/caller/db")
+    assert bench.seed_solver_db() is None and os.environ["MIOPEN_USER_DB_PATH"] == "/caller/db"
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH")
+    d = bench.seed_solver_db()
+    assert os.environ["MIOPEN_USER_DB_PATH"] == d and os.path.realpath(d) != os.path.realpath(bench.SOLVER_DB)
+    assert sorted(os.listdir(d)) == recorded
+
+
 def test_scan_tune_tuple_maps_to_the_struct_encoding():
     """``selective_scan_fwd / _bwd(tune=...)`` -> oss_scan_*_params.tune_* (0 = heuristic, variant + 1; "bf16" -> tune_partials 2)"""
     from vmambair_amd.ops.scan import _tune_fields

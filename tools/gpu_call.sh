@@ -16,7 +16,7 @@ for leg in "${LEG_LIST[@]}"; do
   case $name in
     smoke)  timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1;;
     pytest) timeout ${PYTEST_TIMEOUT:-1800} python -m pytest tests -m gpu -x -q -s -p no:cacheprovider --durations=25 ${PYTEST_ARGS:-} "$@" > $O/${TAG}_pytest.txt 2>&1; echo "rc=$?"; tail -4 $O/${TAG}_pytest.txt; grep -E "^\[|^(FAILED|ERROR)" $O/${TAG}_pytest.txt | cut -c1-240 | tail -60;;
-    bench)  t=${1:-default}; shift; timeout 900 python bench.py "$@" ${BENCH_ARGS:-} > $O/${TAG}_bench_$t.txt 2>$O/${TAG}_bench_$t.err; echo "rc=$?"; tail -1 $O/${TAG}_bench_$t.txt | cut -c1-400;;
+    bench)  t=${1:-default}; shift; timeout 900 python bench.py --full "$@" ${BENCH_ARGS:-} > $O/${TAG}_bench_$t.txt 2>$O/${TAG}_bench_$t.err; echo "rc=$?"; tail -1 $O/${TAG}_bench_$t.txt | cut -c1-400;;
     prof)   t=$1; shift; prof $t "$@";;
     sh)     timeout ${SH_TIMEOUT:-900} bash -c "$*"; echo "rc=$?";;
     *) echo "unknown leg $name";;
