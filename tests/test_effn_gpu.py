@@ -104,8 +104,9 @@ def test_fused_effn_leaves_training_and_unsupported_streams_to_the_chain():
         torch.ops.vmambair.effn_fwd(x.half(), norm.body.weight, norm.body.bias, w_in, ff.dwconv.weight.reshape(254, 9), w_out, 127)
 
 
-def test_rounded_weights_follow_the_parameters():
-    """the module keeps the rounded copies per weight version: an in-place update (an optimizer step, load_state_dict) refreshes them"""
+def test_rounded_weights_are_made_per_call_from_the_live_parameters():
+    """the module rounds its weights on every call (no cache: an update through raw pointers or ``p.data`` bumps no version counter --
+    tests/test_fast_path_state_gpu.py); two calls on unchanged weights give the same copies, an in-place update shows in the next one"""
     torch.manual_seed(7)
     norm = oss_block.LayerNorm(48, "WithBias").to(DEV)
     ff = oss_block.FeedForward(48, 2.66, False).to(DEV)
@@ -113,10 +114,11 @@ def test_rounded_weights_follow_the_parameters():
     with torch.no_grad():
         a = ff(x, pre_norm=norm)
         first = ff._rounded(torch.float16)
-        assert ff._rounded(torch.float16)[0] is first[0]
+        assert all(torch.equal(u, v) for u, v in zip(ff._rounded(torch.float16), first))
         ff.project_out.weight.mul_(2.0)
         b = ff(x, pre_norm=norm)
-    assert ff._rounded(torch.float16)[0] is not first[0]
+    w_out = ff._rounded(torch.float16)[2]
+    assert torch.equal(w_out[:, :127], ff.project_out.weight.detach().reshape(48, 127).half()) and not torch.equal(w_out, first[2])
     assert_close((b.float() - x.float()), 2.0 * (a.float() - x.float()), 5e-3, 5e-3 * float(a.abs().max()), "doubled project_out")
 
 
@@ -138,9 +140,9 @@ def test_round_weights_kernel_matches_the_torch_construction():
 
 
 def test_a_captured_inference_graph_follows_in_place_weight_updates():
-    """the rounded weight copies are cached per weight version in eager mode; inside a graph capture the rounding launch is captured
-    with the forward, so a replay after an in-place update of the parameters (load_state_dict, an optimizer step between two
-    validations) computes with the NEW weights -- as every other kernel of the net does, reading the fp32 parameters directly"""
+    """the rounded weight copies are made per call; inside a graph capture the rounding launch is captured with the forward, so a
+    replay after an in-place update of the parameters (load_state_dict, an optimizer step between two validations) computes with the
+    NEW weights -- as every other kernel of the net does, reading the fp32 parameters directly"""
     torch.manual_seed(9)
     norm = oss_block.LayerNorm(48, "WithBias").to(DEV)
     ff = oss_block.FeedForward(48, 2.66, False).to(DEV)
@@ -149,7 +151,7 @@ def test_a_captured_inference_graph_follows_in_place_weight_updates():
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            ff(x, pre_norm=norm)   # warm-up: fills the eager cache
+            ff(x, pre_norm=norm)   # warm-up outside the capture
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()

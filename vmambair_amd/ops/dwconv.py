@@ -317,7 +317,8 @@ def dwconv3x3_gelu_gate(t: torch.Tensor, conv: torch.nn.Conv2d) -> torch.Tensor:
     """the EFFN between its two 1x1 convolutions: fused when the shape allows, else the two separate nodes"""
     if fused_ok(t, 2):
         return DWGateFn.apply(t, conv.weight, conv.bias)
-    if not (torch.is_grad_enabled() and (t.requires_grad or conv.weight.requires_grad)) and gate_fwd_ok(t):
+    if not (torch.is_grad_enabled() and (t.requires_grad or conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad))) \
+            and gate_fwd_ok(t):
         # inference on planes the backward's LDS-resident form cannot hold (RealSR tiles of 272 x 272, the untiled 512 x 512):
         # the forward streams, so the convolution still is never stored
         return torch.ops.vmambair.dwgate_fwd(t, conv.weight, conv.bias)

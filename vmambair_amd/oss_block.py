@@ -91,25 +91,24 @@ class FeedForward(nn.Module):
         self.project_out = nn.Conv2d(hidden, dim, kernel_size=1, bias=bias)
 
     def _rounded(self, dtype: torch.dtype):
-        """the weights as the one-launch forward reads them, once per weight version (inference: constants) -- ops.ffn.effn_round_weights"""
-        wi, wd, wo = self.project_in.weight, self.dwconv.weight, self.project_out.weight
-        if wi.is_cuda and torch.cuda.is_current_stream_capturing():
-            # inside a graph capture the one-launch rounding is captured too and replayed with the forward: a graph must not bake in
-            # copies that an in-place weight update (load_state_dict, an optimizer step between validations) would leave stale
-            return effn_round_weights(wi, wd, wo, dtype)
-        if wi.is_inference() or wd.is_inference() or wo.is_inference():
-            return effn_round_weights(wi, wd, wo, dtype)   # (inference tensors carry no version counter: nothing to key a cache on)
-        key = (dtype, wi._version, wd._version, wo._version, wi.data_ptr(), wd.data_ptr(), wo.data_ptr())
-        hit = getattr(self, "_rounded_cache", None)
-        if hit is None or hit[0] != key:
-            hit = (key, effn_round_weights(wi, wd, wo, dtype))
-            self._rounded_cache = hit
-        return hit[1]
+        """the weights as the one-launch forward reads them, rounded on EVERY call (one small launch; inside a graph capture it is
+        captured and replayed with the forward) -- ops.ffn.effn_round_weights.  No cache: the fused optimizer step (raw pointers, also
+        replayed from a training graph) and ``p.data`` updates (the reference's model_ema) change the weights without bumping
+        ``_version``, so no key built from the tensors can tell a stale copy from a fresh one"""
+        return effn_round_weights(self.project_in.weight, self.dwconv.weight, self.project_out.weight, dtype)
+
+    def _needs_grad(self, x: torch.Tensor, pre_norm: "LayerNorm") -> bool:
+        """does this forward have to build an autograd graph?  Every tensor it reads counts, not just x and project_in: a partly
+        frozen module (fine-tuning the output projections only) still needs the gradients of its trainable parameters"""
+        if not torch.is_grad_enabled():
+            return False
+        return x.requires_grad or any(p.requires_grad for p in self.parameters()) or \
+            any(p.requires_grad for p in pre_norm.parameters())
 
     def forward(self, x: torch.Tensor, residual: torch.Tensor = None, pre_norm: "LayerNorm" = None) -> torch.Tensor:
         """``pre_norm``: x is the un-normalised stream and the block's norm2 is applied here, fused into project_in; the skip
         connection is then x itself"""
-        if pre_norm is not None and not (torch.is_grad_enabled() and (x.requires_grad or self.project_in.weight.requires_grad)) \
+        if pre_norm is not None and not self._needs_grad(x, pre_norm) \
                 and self.project_in.bias is None and self.dwconv.bias is None and self.project_out.bias is None \
                 and effn_fwd_ok(x, self.project_out.in_channels):
             # inference: norm2 -> project_in -> dwconv -> gate -> project_out -> + x as ONE launch (csrc/oss_effn.hip); the 2h- and
