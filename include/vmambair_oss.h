@@ -629,6 +629,40 @@ int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *d
                            int cout, int height, int width, int64_t x_batch_stride, int64_t x_channel_stride, int64_t dy_batch_stride,
                            int64_t dy_channel_stride, oss_stream_t stream);
 
+/* The reference's validation metrics of a batch of image pairs, on the device, in one call: the mean squared error behind
+ * calculate_psnr (Deraining/basicsr/metrics/psnr_ssim.py:9-63) and the mean SSIM of _ssim (psnr_ssim.py:66-99; Deraining/Deraining/
+ * utils.py:31-78) or _ssim_cly (psnr_ssim.py:184-222), with 11 x 11 Gaussian window (sigma 1.5), C1 = (0.01 * 255)^2,
+ * C2 = (0.03 * 255)^2, all moments and the quotient in fp64.
+ *   a, b      (batch, channels, height, width), channels 1 or 3 in R, G, B order, element strides for batch / channel / row, column
+ *             stride 1 (cropped views need no copy); io = fp32 / fp16 / bf16
+ *   out       (batch, 2) doubles: mean squared error over the cropped planes, mean SSIM.  PSNR = 10 log10(255^2 / mse)
+ *   partials  oss_image_metrics_partial_doubles(...) doubles of scratch, no init: one (squared error, SSIM sum) pair per workgroup,
+ *             added in a fixed order by a second small launch of the same call -- no atomics, reruns are bit-identical, no host
+ *             read-back, capturable into a hipGraph
+ *   crop_border pixels are dropped on every side first (psnr_ssim.py:46-48, :276-278)
+ *   flags     OSS_METRIC_QUANTISE   the values are network outputs in [0, 1]: clamp, * 255, round half to even on load, in fp32
+ *                                   (tensor2img, SRGAN/VmambaIR/utils/img_util.py:68-92); clear: already in [0, 255] units
+ *             OSS_METRIC_Y          channels == 3 only: both metrics on the BT.601 luma of to_y_channel (metrics/metric_util.py:
+ *                                   34-47, utils/matlab_functions.py:207-238): / 255 in fp32, dot product in fp64, + 16, / 255, cast
+ *                                   to fp32, * 255; the squared difference is then taken in fp32 and summed in fp64 as
+ *                                   calculate_psnr does.  Clear with 3 channels: the mean over the three per-channel SSIMs
+ *                                   (utils.calculate_ssim:46-51) and the squared error over all three
+ *             OSS_METRIC_REPLICATE  every cropped pixel is a window centre, neighbours outside the cropped plane are clamped to its
+ *                                   edge (_ssim_cly, cv2.BORDER_REPLICATE); clear: only the (height' - 10)(width' - 10) windows
+ *                                   inside the cropped plane (_ssim), which needs height', width' >= 11
+ * oss_image_metrics_ok is a pure host query: 1 when the shape and flags are taken.  OSS_ERR_NULL for a NULL pointer, OSS_ERR_SHAPE
+ * for channels not in {1, 3}, Y with one channel, crop_border >= half a side, valid mode on a cropped plane under 11 pixels, or a
+ * launch grid beyond the device limits (batch * planes > 65535, height' > 16 * 65535). */
+#define OSS_METRIC_QUANTISE 1
+#define OSS_METRIC_Y 2
+#define OSS_METRIC_REPLICATE 4
+int oss_image_metrics_ok(oss_dtype io, int channels, int height, int width, int crop_border, int flags);
+size_t oss_image_metrics_partial_doubles(int batch, int channels, int height, int width, int crop_border);
+int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, double *partials, int batch, int channels,
+                      int height, int width, int64_t a_batch_stride, int64_t a_channel_stride, int64_t a_row_stride,
+                      int64_t b_batch_stride, int64_t b_channel_stride, int64_t b_row_stride, int crop_border, int flags,
+                      oss_stream_t stream);
+
 /* Algorithmic bytes of the block's NON-scan launches, by kernel family (round 6; bench.py `roofline.non_scan`).  While counting
  * is on, every entry point of this header that launches a kernel adds the bytes its launch must move at minimum (each operand
  * read once, each result written once, fp32 master weights included, scratch partials not) to its family's counter -- host-side

@@ -11,6 +11,7 @@ import os
 from . import _build
 
 OSS_F32, OSS_F16, OSS_BF16 = 0, 1, 2
+METRIC_QUANTISE, METRIC_Y, METRIC_REPLICATE = 1, 2, 4   # flags of oss_image_metrics
 FEATURE_FUSED_DT, FEATURE_LANE_STATES = 1, 2   # oss_scan_features(): runtime-selected scan forms (in every library since round 6)
 
 ERRORS = {
@@ -89,7 +90,7 @@ SYMBOLS = ["oss_scan_chunk", "oss_scan_num_chunks", "oss_scan_fwd", "oss_scan_fw
            "oss_gelu_gate_bwd", "oss_adam_ema_step", "oss_adamw_ema_step", "oss_set_defer_finish", "oss_deferred_chunks",
            "oss_flush_finishes", "oss_flush_finishes_n", "oss_flush_wgrads_n", "oss_set_defer_wgrad", "oss_deferred_wgrads", "oss_deferred_wgrad_table_bytes", "oss_flush_wgrads",
            "oss_conv3x3_thin_ok", "oss_conv3x3_thin_fwd", "oss_conv3x3_thin_dgrad", "oss_conv3x3_thin_wgrad_partial_floats",
-           "oss_conv3x3_thin_wgrad", "oss_hbm_copy", "oss_prof_marker", "oss_scan_build_id", "oss_version", "oss_scan_features", "oss_abi_version", "oss_abi_struct_bytes"]
+           "oss_conv3x3_thin_wgrad", "oss_image_metrics_ok", "oss_image_metrics_partial_doubles", "oss_image_metrics", "oss_hbm_copy", "oss_prof_marker", "oss_scan_build_id", "oss_version", "oss_scan_features", "oss_abi_version", "oss_abi_struct_bytes"]
 
 #: include/vmambair_oss.h: OSS_ABI_VERSION this binding was written against
 ABI_VERSION = 7
@@ -286,6 +287,12 @@ def load():
     lib.oss_conv3x3_thin_wgrad_partial_floats.argtypes = [C.c_int] * 3
     lib.oss_conv3x3_thin_wgrad.restype = C.c_int
     lib.oss_conv3x3_thin_wgrad.argtypes = [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_int64] * 4 + [C.c_void_p]
+    lib.oss_image_metrics_ok.restype = C.c_int
+    lib.oss_image_metrics_ok.argtypes = [C.c_int] * 6
+    lib.oss_image_metrics_partial_doubles.restype = C.c_size_t
+    lib.oss_image_metrics_partial_doubles.argtypes = [C.c_int] * 5
+    lib.oss_image_metrics.restype = C.c_int
+    lib.oss_image_metrics.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_int64] * 6 + [C.c_int, C.c_int, C.c_void_p]
     lib.oss_hbm_copy.restype = C.c_int
     lib.oss_hbm_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.oss_prof_marker.restype = C.c_int

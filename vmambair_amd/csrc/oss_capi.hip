@@ -666,6 +666,20 @@ int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *d
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+int oss_image_metrics_ok(oss_dtype io, int channels, int height, int width, int crop_border, int flags) {
+    return image_metrics_ok(io, channels, height, width, crop_border, flags);
+}
+size_t oss_image_metrics_partial_doubles(int batch, int channels, int height, int width, int crop_border) {
+    return image_metrics_partial_doubles(batch, channels, height, width, crop_border);
+}
+int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, double *partials, int batch, int channels, int height,
+                      int width, int64_t asb, int64_t asc, int64_t ars, int64_t bsb, int64_t bsc, int64_t brs, int crop_border, int flags,
+                      oss_stream_t stream) {
+    if (!a || !b || !out || !partials) return OSS_ERR_NULL;
+    return image_metrics(io, a, b, out, partials, batch, channels, height, width, asb, asc, ars, bsb, bsc, brs, crop_border, flags,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 void oss_set_defer_wgrad(int on) {
     std::lock_guard<std::mutex> lk(g_defer_mu);
     g_defer_wgrad.store(on ? 1 : 0);

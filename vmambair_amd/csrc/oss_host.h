@@ -189,5 +189,10 @@ void defer_sum(const float *src, int K, size_t stride, size_t V, float *dst0, si
 int sum_partials_multi(const oss_sum_chunk *chunks, int n_chunks, hipStream_t s);
 int adam_ema_step(const oss_adam_chunk *chunks, int n_chunks, float *state, float lr, float beta1, float beta2, float eps,
                   float ema_decay, hipStream_t s, float weight_decay = 0.f, const float *grad_scale = nullptr);
+// PSNR + SSIM of a batch of image pairs (oss_metrics.hip)
+int image_metrics_ok(oss_dtype io, int C, int H, int W, int crop, int flags);
+size_t image_metrics_partial_doubles(int B, int C, int H, int W, int crop);
+int image_metrics(oss_dtype io, const void *a, const void *b, double *out, double *part, int B, int C, int H, int W, int64_t asb,
+                  int64_t asc, int64_t ars, int64_t bsb, int64_t bsc, int64_t brs, int crop, int flags, hipStream_t s);
 int scan_fwd_pick_variant(int batch, int dim, int seqlen, int dstate, int n_groups, int elem_bytes);
 }  // namespace oss
