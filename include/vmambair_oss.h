@@ -45,7 +45,19 @@ extern "C" {
 
 /* I/O element type of u, delta, B, C, out, dout, du, ddelta (the reference's input_t);
  * A, D, delta_bias, x and every weight gradient are always float (weight_t). */
-typedef enum { OSS_F32 = 0, OSS_F16 = 1, OSS_BF16 = 2 } oss_dtype;
+typedef enum {
+    OSS_F32 = 0, OSS_F16 = 1, OSS_BF16 = 2,
+    /* (ABI 8) NOT an element type but a per-call precision selector: "fp32 tensors, products on split bf16".  Accepted by exactly six
+     * entry points -- oss_conv1x1_fwd / _dgrad / _wgrad, oss_proj_fwd / _dgrad / _wgrad -- where it means OSS_F32 tensors whose
+     * GEMM-shaped products run on v_mfma_f32_32x32x16_bf16 with each fp32 operand value a taken as hi + lo, hi = bf16(a),
+     * lo = bf16(a - hi) (lo = 0 where a - hi is not finite), three products per pair (lo hi, hi lo, hi hi; lo lo is dropped) into
+     * one fp32 accumulator, fp32 epilogues:  |y - y_exact| <= (3 * 2^-16 + (K + 2) * 2^-23) * sum_k |w_k||x_k|.  gfx950 has no
+     * xf32 / TF32 matrix instruction; this is what torch.set_float32_matmul_precision("high") describes.  Same shapes, alignment
+     * rules, scratch sizes and error returns as OSS_F32; calls the exact fp32 matrix-core kernels decline (and that then run on
+     * the vector-ALU kernels) are not affected by the selector.  Deterministic (fixed summation order, no atomics).  Every other
+     * entry point rejects the value (OSS_ERR_SHAPE, or 0 from an *_ok query).  oss_f32_matmul_modes() & 2 says the library has it. */
+    OSS_F32_BF16X3 = 3
+} oss_dtype;
 
 /* Opaque stream handle: a hipStream_t (NULL = the default stream). */
 typedef void *oss_stream_t;
@@ -683,13 +695,18 @@ int oss_prof_family(int family, const char **name, const char **kernel_patterns,
 #define OSS_FEATURE_LANE_STATES 2
 int oss_scan_features(void);
 
+/* fp32 product modes of the six GEMM-shaped entry points (pure host query): bit 0 = exact fp32 MFMA (OSS_F32), bit 1 = split bf16
+ * (OSS_F32_BF16X3). */
+int oss_f32_matmul_modes(void);
+
 /* ABI guard.  oss_scan_fwd_params / oss_scan_bwd_params / oss_chan_params cross the boundary BY POINTER, so a binding layer
  * compiled against another revision of this header would hand the kernels garbage pointers.  OSS_ABI_VERSION is bumped with
- * every change of a struct or of an entry point's argument list; oss_abi_struct_bytes(which) is the library's own sizeof
+ * every change of a struct or of an entry point's argument list (8: the value OSS_F32_BF16X3 of oss_dtype and
+ * oss_f32_matmul_modes(); no struct changed); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree (vmambair_amd/_capi.py, csrc_host/oss_torch_host.cpp through vmambair_amd/_host.py) compares both with its
  * own compile-time values when it loads and refuses to run on a mismatch. */
-#define OSS_ABI_VERSION 7
+#define OSS_ABI_VERSION 8
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Order of loads / stores / waits / MFMAs / barriers of one kernel in /tmp/isa/<tu>.s (written by tools/kernel_regs.py):
-    python tools/isa_seq.py oss_conv1x1_f32 'oss_conv1x1_f32_kernel<1, true>'
+    python tools/isa_seq.py oss_conv1x1_f32 'oss_conv1x1_f32_kernel<1, true, false>'
 L = global load, S = global store, wN = s_waitcnt vmcnt(N), M = MFMA, D = LDS op, B = s_barrier, j = branch, | = label; runs compressed."""
 import re
 import subprocess

@@ -37,11 +37,32 @@ def timeit(fn, reps=20, replays=5, warm=3):
     return a.elapsed_time(b) * 1000.0 / (reps * replays)
 
 
+def f32_matmul():
+    """fp32 1x1 convolutions at batch 8, 64 x 64: "highest" (v_mfma_f32_32x32x2_f32) next to "high" (three v_mfma_f32_32x32x16_bf16
+    on split operands; vmambair_amd.set_float32_matmul_precision).  The graph of a timing is captured under its mode."""
+    import vmambair_amd
+    torch.manual_seed(0)
+    B, H = 8, 64
+    for ci, co in [(48, 96), (96, 255 * 2), (255, 96)]:
+        x = torch.randn(B, ci, H, H, device=DEV)
+        w = torch.randn(co, ci, 1, 1, device=DEV) / ci ** 0.5
+        dy = torch.randn(B, co, H, H, device=DEV)
+        for mode in ("highest", "high"):
+            with vmambair_amd.float32_matmul_precision(mode):
+                fwd = timeit(lambda: ops.conv1x1_fwd(x, w, None))
+                bwd = timeit(lambda: ops.conv1x1_bwd(x, w, dy, False))
+            print(f"(8, {ci}->{co}, 64x64) fp32 {mode:8s} fwd {fwd:8.1f} us   dgrad + wgrad {bwd:8.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--f32-matmul", action="store_true",
+                    help="only the fp32 1x1 convolutions under both precision modes (exact fp32 MFMA | split bf16)")
     args = ap.parse_args()
+    if args.f32_matmul:
+        return f32_matmul()
     dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[args.dtype]
     torch.manual_seed(0)
     B = 8

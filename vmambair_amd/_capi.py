@@ -11,6 +11,9 @@ import os
 from . import _build
 
 OSS_F32, OSS_F16, OSS_BF16 = 0, 1, 2
+#: per-call selector of the six GEMM-shaped entry points: fp32 tensors, products on split bf16 (include/vmambair_oss.h)
+OSS_F32_BF16X3 = 3
+F32_MODE_EXACT, F32_MODE_BF16X3 = 1, 2   # bits of oss_f32_matmul_modes()
 METRIC_QUANTISE, METRIC_Y, METRIC_REPLICATE = 1, 2, 4   # flags of oss_image_metrics
 FEATURE_FUSED_DT, FEATURE_LANE_STATES = 1, 2   # oss_scan_features(): runtime-selected scan forms (in every library since round 6)
 
@@ -90,10 +93,10 @@ SYMBOLS = ["oss_scan_chunk", "oss_scan_num_chunks", "oss_scan_fwd", "oss_scan_fw
            "oss_gelu_gate_bwd", "oss_adam_ema_step", "oss_adamw_ema_step", "oss_set_defer_finish", "oss_deferred_chunks",
            "oss_flush_finishes", "oss_flush_finishes_n", "oss_flush_wgrads_n", "oss_set_defer_wgrad", "oss_deferred_wgrads", "oss_deferred_wgrad_table_bytes", "oss_flush_wgrads",
            "oss_conv3x3_thin_ok", "oss_conv3x3_thin_fwd", "oss_conv3x3_thin_dgrad", "oss_conv3x3_thin_wgrad_partial_floats",
-           "oss_conv3x3_thin_wgrad", "oss_image_metrics_ok", "oss_image_metrics_partial_doubles", "oss_image_metrics", "oss_hbm_copy", "oss_prof_marker", "oss_scan_build_id", "oss_version", "oss_scan_features", "oss_abi_version", "oss_abi_struct_bytes"]
+           "oss_conv3x3_thin_wgrad", "oss_image_metrics_ok", "oss_image_metrics_partial_doubles", "oss_image_metrics", "oss_hbm_copy", "oss_prof_marker", "oss_scan_build_id", "oss_version", "oss_scan_features", "oss_f32_matmul_modes", "oss_abi_version", "oss_abi_struct_bytes"]
 
 #: include/vmambair_oss.h: OSS_ABI_VERSION this binding was written against
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lib = None
 
@@ -303,6 +306,8 @@ def load():
         raise RuntimeError(f"{path} predates the ABI guard of include/vmambair_oss.h: rebuild it (__graft_entry__.build())")
     lib.oss_abi_version.restype = C.c_int
     lib.oss_scan_features.restype = C.c_int
+    lib.oss_f32_matmul_modes.restype = C.c_int
+    lib.oss_f32_matmul_modes.argtypes = []
     lib.oss_abi_struct_bytes.restype = C.c_size_t
     lib.oss_abi_struct_bytes.argtypes = [C.c_int]
     # the structs cross the boundary by pointer: a library built from another revision of the header would misread them

@@ -200,6 +200,15 @@ static std::atomic<int> g_fam_on{0};
 static double g_fam_bytes[FAM_N];
 static long long g_fam_calls[FAM_N];
 static inline int esz(oss_dtype io) { return io == OSS_F32 ? 4 : 2; }
+// OSS_F32_BF16X3 is a per-call selector, not an element type: the six entry points that accept it turn it into OSS_F32 plus a flag
+// before anything looks at `io` (esz() above and most dispatchers read every value that is not OSS_F32 as a 2-byte type)
+// (every OTHER entry point with an oss_dtype argument opens with `if (is_f32_split(io)) return <its dtype error>;`)
+static inline bool is_f32_split(oss_dtype io) { return io == OSS_F32_BF16X3; }
+static inline int take_f32_split(oss_dtype &io) {
+    if (!is_f32_split(io)) return 0;
+    io = OSS_F32;
+    return 1;
+}
 static inline void fam_count(int fam, double bytes) {
     if (!g_fam_on.load(std::memory_order_relaxed)) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -254,6 +263,7 @@ int oss_scan_chunk(void) { return kScanChunk; }
 int oss_scan_num_chunks(int seqlen) { return seqlen <= 0 ? 0 : (seqlen + kScanChunk - 1) / kScanChunk; }
 
 int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     int rc = check_fwd(p);
     if (rc != OSS_OK) return rc;
     if (!p->out || !p->x) return OSS_ERR_NULL;
@@ -314,6 +324,7 @@ size_t oss_scan_fwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, 
 int oss_scan_bwd_finish_dt_ok(int seqlen, int dt_rank) { return scan_finish_dt_ok(seqlen, dt_rank) ? 1 : 0; }
 
 int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     if (!p) return OSS_ERR_NULL;
     int rc = check_fwd(&p->f);
     if (rc != OSS_OK) return rc;
@@ -336,6 +347,7 @@ int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream
         case OSS_F32: return scan_bwd_dispatch<float>(*p, v, sr, s, &prof, &fprof);
         case OSS_F16: return scan_bwd_dispatch<f16_t>(*p, v, sr, s, &prof, &fprof);
         case OSS_BF16: return scan_bwd_dispatch<bf16_t>(*p, v, sr, s, &prof, &fprof);
+        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
     }
     return OSS_ERR_SHAPE;
 }
@@ -343,6 +355,7 @@ int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream
 int oss_dwconv3x3_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, void *pre_silu, int batch,
                       int channels, int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, int flip,
                       oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * (pre_silu ? 3.0 : 2.0) + 40.0 * channels);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
@@ -351,11 +364,13 @@ int oss_dwconv3x3_fwd(oss_dtype io, const void *x, const float *weight, const fl
 }
 
 int oss_dwconv3x3_fused_ok(oss_dtype io, int height, int width, int channels_per_workgroup) {
+    if (is_f32_split(io)) return 0;
     return dwconv3x3_fused_ok(io, height, width, channels_per_workgroup);
 }
 
 int oss_dwconv3x3_silu_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int channels,
                            int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 2.0 + 40.0 * channels);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
@@ -366,6 +381,7 @@ int oss_dwconv3x3_silu_fwd(oss_dtype io, const void *x, const float *weight, con
 int oss_dwconv3x3_silu_bwd(oss_dtype io, const void *x, const float *weight, const float *bias, const void *dy, void *dx,
                            float *dweight, float *dbias, float *partials, int batch, int channels, int height, int width,
                            int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + 80.0 * channels);
     if (!x || !weight || !dy || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
@@ -373,10 +389,14 @@ int oss_dwconv3x3_silu_bwd(oss_dtype io, const void *x, const float *weight, con
                                gsb, gsc, dsb, dsc, reinterpret_cast<hipStream_t>(stream));
 }
 
-int oss_dwconv3x3_flat2_ok(oss_dtype io, int height, int width) { return dwconv3x3_flat2_ok(io, height, width); }
+int oss_dwconv3x3_flat2_ok(oss_dtype io, int height, int width) {
+    if (is_f32_split(io)) return 0;
+    return dwconv3x3_flat2_ok(io, height, width);
+}
 
 int oss_dwconv3x3_silu_flat2_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *x2, int batch, int channels,
                                  int height, int width, int64_t xsb, int64_t xsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + 40.0 * channels);
     if (!x || !weight || !x2) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
@@ -386,6 +406,7 @@ int oss_dwconv3x3_silu_flat2_fwd(oss_dtype io, const void *x, const float *weigh
 int oss_dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *weight, const float *bias, const void *g2, void *dx,
                                  float *dweight, float *dbias, float *partials, int batch, int channels, int height, int width,
                                  int64_t xsb, int64_t xsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 4.0 + 80.0 * channels);
     if (!x || !weight || !g2 || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
@@ -393,10 +414,14 @@ int oss_dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *weigh
                                     dsc, reinterpret_cast<hipStream_t>(stream));
 }
 
-int oss_effn_fwd_ok(oss_dtype io, int channels, int hidden, int height, int width) { return effn_fwd_ok(io, channels, hidden, height, width); }
+int oss_effn_fwd_ok(oss_dtype io, int channels, int hidden, int height, int width) {
+    if (is_f32_split(io)) return 0;
+    return effn_fwd_ok(io, channels, hidden, height, width);
+}
 
 int oss_effn_round_weights(oss_dtype io, const float *project_in, const float *dwconv, const float *project_out, void *w_in, float *w_dw,
                            void *w_out, int channels, int hidden, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     if (!project_in || !dwconv || !project_out || !w_in || !w_dw || !w_out) return OSS_ERR_NULL;
     return effn_round_weights(io, project_in, dwconv, project_out, w_in, w_dw, w_out, channels, hidden, reinterpret_cast<hipStream_t>(stream));
 }
@@ -404,6 +429,7 @@ int oss_effn_round_weights(oss_dtype io, const float *project_in, const float *d
 int oss_effn_fwd(oss_dtype io, const void *x, const float *norm_weight, const float *norm_bias, const void *w_in, const float *w_dw,
                  const void *w_out, void *out, int batch, int channels, int hidden, int height, int width, int64_t xsb, int64_t xsc,
                  int64_t osb, int64_t osc, float eps, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + (double)hidden * (3.0 * channels * esz(io) + 72.0));
     if (!x || !norm_weight || !w_in || !w_dw || !w_out || !out) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || hidden <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
@@ -411,10 +437,14 @@ int oss_effn_fwd(oss_dtype io, const void *x, const float *norm_weight, const fl
                     reinterpret_cast<hipStream_t>(stream));
 }
 
-int oss_dwgate_fwd_ok(oss_dtype io, int height, int width) { return dwgate_fwd_ok(io, height, width); }
+int oss_dwgate_fwd_ok(oss_dtype io, int height, int width) {
+    if (is_f32_split(io)) return 0;
+    return dwgate_fwd_ok(io, height, width);
+}
 
 int oss_dwgate_fwd(oss_dtype io, const void *t, const float *weight, const float *bias, void *out, int batch, int hidden,
                    int height, int width, int64_t tsb, int64_t tsc, int64_t osb, int64_t osc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * hidden * height * width * esz(io) * 3.0 + 80.0 * hidden);
     if (!t || !weight || !out) return OSS_ERR_NULL;
     if (batch <= 0 || hidden <= 0 || height <= 0 || width <= 0 || hidden > 32767 || batch > 65535) return OSS_ERR_SHAPE;
@@ -424,6 +454,7 @@ int oss_dwgate_fwd(oss_dtype io, const void *t, const float *weight, const float
 int oss_dwgate_bwd(oss_dtype io, const void *t, const float *weight, const float *bias, const void *dout, void *dt,
                    float *dweight, float *dbias, float *partials, int batch, int hidden, int height, int width, int64_t tsb,
                    int64_t tsc, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * hidden * height * width * esz(io) * 5.0 + 160.0 * hidden);
     if (!t || !weight || !dout || !dt || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || hidden <= 0 || height <= 0 || width <= 0 || hidden > 32767 || batch > 65535) return OSS_ERR_SHAPE;
@@ -434,6 +465,7 @@ int oss_dwgate_bwd(oss_dtype io, const void *t, const float *weight, const float
 int oss_dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dweight, float *dbias, float *partials,
                         const void *pre_silu, void *dpre, int batch, int channels, int height, int width, int64_t xsb,
                         int64_t xsc, int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * (pre_silu ? 4.0 : 2.0));
     if (!x || !dy || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || batch > 65535) return OSS_ERR_SHAPE;
@@ -443,20 +475,22 @@ int oss_dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dwei
 
 int oss_conv1x1_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, const void *residual, void *y,
                     int batch, int cout, int cin, int pixels, int64_t xsb, int64_t xsc, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout + (residual ? cout : 0)) + 4.0 * cin * cout);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535 || cout > 32 * 65535) return OSS_ERR_SHAPE;
     return conv1x1(io, x, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, cin, 1, reinterpret_cast<hipStream_t>(stream),
-                   residual);
+                   residual, x3);
 }
 
 int oss_conv1x1_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cout, int cin, int pixels,
                       int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!dy || !weight || !dx) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     // dx[ci] = sum_co W[co][ci] dy[co]: the same GEMM with the weights read transposed
-    return conv1x1(io, dy, weight, nullptr, dx, batch, cin, cout, pixels, gsb, gsc, 1, cin, reinterpret_cast<hipStream_t>(stream));
+    return conv1x1(io, dy, weight, nullptr, dx, batch, cin, cout, pixels, gsb, gsc, 1, cin, reinterpret_cast<hipStream_t>(stream), nullptr, x3);
 }
 
 size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels) {
@@ -466,11 +500,12 @@ size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels
 
 int oss_conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dweight, float *dbias, float *partials, int batch,
                       int cout, int cin, int pixels, int64_t gsb, int64_t gsc, int64_t xsb, int64_t xsc, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_WGRAD, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!dy || !x || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return conv1x1_wgrad(io, dy, x, dweight, partials, batch, cout, cin, pixels, gsb, gsc, xsb, xsc,
-                         reinterpret_cast<hipStream_t>(stream), 1, 0, 0, 0, 0, dbias);
+                         reinterpret_cast<hipStream_t>(stream), 1, 0, 0, 0, 0, dbias, x3);
 }
 
 size_t oss_proj_wgrad_partial_floats(int batch, int D, int C, int R, int seqlen) {
@@ -483,30 +518,35 @@ size_t oss_proj_wgrad_partial_floats(int batch, int D, int C, int R, int seqlen)
 
 int oss_proj_fwd(oss_dtype io, const void *x2, const float *x_proj_weight, const float *dt_projs_weight, void *xdbl, void *dts,
                  int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_PROJ, (double)batch * seqlen * esz(io) * (2.0 * D + 4.0 * C + (dts ? 4.0 * R + 4.0 * D : 0.0)) + 16.0 * C * D + 16.0 * D * R);
     if (!x2 || !x_proj_weight || !dt_projs_weight || !xdbl) return OSS_ERR_NULL;   // dts == NULL: fused-delta form
     if (batch <= 0 || D <= 0 || seqlen <= 0 || R <= 0 || C <= R) return OSS_ERR_SHAPE;
-    return proj_fwd(io, x2, x_proj_weight, dt_projs_weight, xdbl, dts, batch, D, C, R, seqlen, reinterpret_cast<hipStream_t>(stream));
+    return proj_fwd(io, x2, x_proj_weight, dt_projs_weight, xdbl, dts, batch, D, C, R, seqlen, reinterpret_cast<hipStream_t>(stream), x3);
 }
 
 int oss_proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, const float *x_proj_weight,
                    const float *dt_projs_weight, void *dx2, int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_PROJ, (double)batch * seqlen * esz(io) * ((ddts ? 4.0 * D + 4.0 * R : 0.0) + 4.0 * C + (du ? 4.0 * D : 0.0) + 2.0 * D) + 16.0 * C * D);
     if (!dxdbl || !x_proj_weight || !dt_projs_weight || !dx2) return OSS_ERR_NULL;   // ddts == NULL: fused-delta form
     if (batch <= 0 || D <= 0 || seqlen <= 0 || R <= 0 || C <= R) return OSS_ERR_SHAPE;
     return proj_dgrad(io, ddts, dxdbl, du, x_proj_weight, dt_projs_weight, dx2, batch, D, C, R, seqlen,
-                      reinterpret_cast<hipStream_t>(stream));
+                      reinterpret_cast<hipStream_t>(stream), x3);
 }
 
 void oss_proj_set_path(int force_vector_alu) { proj_force_valu(force_vector_alu); }
 int oss_proj_rows_optional_ok(oss_dtype io, int batch, int D, int C, int R, int seqlen) {
+    if (is_f32_split(io)) return 0;
     return proj_mfma_ok(io, batch, D, C, R, seqlen) ? 1 : 0;
 }
 int oss_scan_fused_dt_ok(oss_dtype io, int batch, int D, int C, int R, int dstate, int seqlen) {
+    if (is_f32_split(io)) return 0;
     return kBuildFusedDt && proj_mfma_ok(io, batch, D, C, R, seqlen) && R >= 1 && R <= kMaxDtRank && dstate <= 64 && seqlen >= 512;
 }
 int oss_conv1x1_wg(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cout, int cin,
                    int pixels, int64_t xsb, int64_t xsc, int transposed_weight, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
@@ -514,6 +554,7 @@ int oss_conv1x1_wg(oss_dtype io, const void *x, const float *weight, const float
 }
 
 int oss_ln_conv1x1_ok(oss_dtype io, int cout, int cin, int pixels) {
+    if (is_f32_split(io)) return 0;
     static const float dummy = 0.f;   // shape / dtype rules only: an aligned stand-in for the pointers
     const void *a = reinterpret_cast<const void *>(uintptr_t(256));
     (void)dummy;
@@ -523,6 +564,7 @@ int oss_ln_conv1x1_ok(oss_dtype io, int cout, int cin, int pixels) {
 int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, const float *ln_bias, float eps, void *n, float *mean,
                        float *rstd, const float *weight, const float *bias, void *y, int batch, int cout, int cin, int pixels,
                        int64_t xsb, int64_t xsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV1X1, (double)batch * pixels * (esz(io) * (2.0 * cin + cout) + 8.0) + 4.0 * cin * cout);
     if (!x || !ln_weight || !n || !mean || !rstd || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
@@ -531,6 +573,7 @@ int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, cons
 }
 
 int oss_conv1x1_dgrad_ln_bwd_ok(oss_dtype io, int cout, int cin, int pixels, int batch) {
+    if (is_f32_split(io)) return 0;
     return conv1x1_dgrad_lnbwd_ok(io, cin, cout, pixels, batch);
 }
 size_t oss_conv1x1_dgrad_ln_bwd_partial_floats(int batch, int cin, int pixels) {
@@ -540,6 +583,7 @@ size_t oss_conv1x1_dgrad_ln_bwd_partial_floats(int batch, int cin, int pixels) {
 int oss_conv1x1_dgrad_ln_bwd(oss_dtype io, const void *dy, const float *weight, const void *x, const float *ln_weight, int ln_has_bias,
                              const float *mean, const float *rstd, const void *skip_grad, void *dx, float *dln_weight, float *dln_bias,
                              float *partials, int batch, int cout, int cin, int pixels, int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV1X1, (double)batch * pixels * (esz(io) * ((double)cout + 2.0 * cin + (skip_grad ? cin : 0)) + 8.0) + 4.0 * cin * cout);
     if (!dy || !weight || !x || !ln_weight || !mean || !rstd || !dx || !dln_weight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
@@ -553,6 +597,7 @@ void oss_conv1x1_wgrad_set_span(int mult) { conv1x1_wgrad_set_span(mult); }
 
 int oss_proj_wgrad(oss_dtype io, const void *x2, const void *xdbl, const void *dxdbl, const void *ddts, float *dx_proj_weight,
                    float *ddt_projs_weight, float *partials, int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
+    const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
     fam_count(FAM_WGRAD, (double)batch * seqlen * esz(io) * (2.0 * D + 8.0 * C + (ddts ? 4.0 * D : 0.0)));
     if (!x2 || !xdbl || !dxdbl || !dx_proj_weight || !partials) return OSS_ERR_NULL;
     if (ddts && !ddt_projs_weight) return OSS_ERR_NULL;   // ddts == NULL: the scan backward produced ddt_projs_weight itself
@@ -562,12 +607,12 @@ int oss_proj_wgrad(oss_dtype io, const void *x2, const void *xdbl, const void *d
     if (io == OSS_F32) {   // fp32 I/O: both products on the fp32 matrix-core kernel (oss_conv1x1_f32.hip), same scratch regions
         // dx_proj_weight[k][c][d] = sum_{b,l} dxdbl[b, k, c, l] x2[b, k % 2, d, l]
         int e = rows_f32_wgrad(reinterpret_cast<const float *>(dxdbl), reinterpret_cast<const float *>(x2), dx_proj_weight, partials, batch,
-                               4, 2, C, D, seqlen, 4 * C * L, C * L, L, 2 * D * L, D * L, L, s);
+                               4, 2, C, D, seqlen, 4 * C * L, C * L, L, 2 * D * L, D * L, L, s, nullptr, x3);
         if (e || !ddts) return e;
         // ddt_projs_weight[k][d][r] = sum_{b,l} ddts[b, k, d, l] xdbl[b, k, r, l]
         float *part2 = partials + (size_t)batch * conv1x1_wgrad_slabs(seqlen) * 2 * (2 * (size_t)C) * D;
         return rows_f32_wgrad(reinterpret_cast<const float *>(ddts), reinterpret_cast<const float *>(xdbl), ddt_projs_weight, part2, batch, 4,
-                              4, D, R, seqlen, 4 * D * L, D * L, L, 4 * C * L, C * L, L, s);
+                              4, D, R, seqlen, 4 * D * L, D * L, L, 4 * C * L, C * L, L, s, nullptr, x3);
     }
     // x_proj_weight: one problem per flattening j; its 2C rows are the rows of directions j and j + 2 of dxdbl
     int e = conv1x1_wgrad(io, dxdbl, x2, dx_proj_weight, partials, batch, 2 * C, D, seqlen, 4 * C * L, L, 2 * D * L, L, s,
@@ -581,6 +626,7 @@ int oss_proj_wgrad(oss_dtype io, const void *x2, const void *xdbl, const void *d
 
 int oss_cross_scan2(oss_dtype in_type, oss_dtype out_type, const void *x, void *x2, int batch, int D, int height, int width,
                     int64_t x_batch_stride, int64_t x_channel_stride, oss_stream_t stream) {
+    if (is_f32_split(in_type) || is_f32_split(out_type)) return OSS_ERR_SHAPE;
     fam_count(FAM_MERGE, (double)batch * D * height * width * (esz(in_type) + 2.0 * esz(out_type)));
     if (!x || !x2) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
@@ -589,6 +635,7 @@ int oss_cross_scan2(oss_dtype in_type, oss_dtype out_type, const void *x, void *
 }
 
 int oss_cross_merge2(oss_dtype io, const void *g2, void *dx, int batch, int D, int height, int width, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_MERGE, (double)batch * D * height * width * esz(io) * 3.0);
     if (!g2 || !dx) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
@@ -612,6 +659,7 @@ int oss_chan_bwd(const oss_chan_params *p, const float *gc, float *dpooled, floa
 
 int oss_rowsum(oss_dtype io, const void *a, const void *bmul, float *out, int batch, int channels, int pixels, int64_t asb,
                int64_t asc, int64_t bsb, int64_t bsc, float alpha, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CHAN, (double)batch * channels * pixels * esz(io) * (bmul ? 2.0 : 1.0));
     if (!a || !out) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0) return OSS_ERR_SHAPE;
@@ -620,6 +668,7 @@ int oss_rowsum(oss_dtype io, const void *a, const void *bmul, float *out, int ba
 
 int oss_row_affine(oss_dtype io, const void *x, const float *mul, const float *add, void *y, int batch, int channels, int pixels,
                    int64_t xsb, int64_t xsc, float alpha, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CHAN, (double)batch * channels * pixels * esz(io) * 2.0);
     if (!x || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0) return OSS_ERR_SHAPE;
@@ -628,6 +677,7 @@ int oss_row_affine(oss_dtype io, const void *x, const float *mul, const float *a
 
 int oss_gelu_gate_fwd(oss_dtype io, const void *h, void *out, int batch, size_t half_elems, int64_t h_batch_stride,
                       oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_GATE, (double)batch * half_elems * esz(io) * 3.0);
     if (!h || !out) return OSS_ERR_NULL;
     if (batch <= 0 || half_elems == 0) return OSS_ERR_SHAPE;
@@ -636,21 +686,27 @@ int oss_gelu_gate_fwd(oss_dtype io, const void *h, void *out, int batch, size_t 
 
 int oss_gelu_gate_bwd(oss_dtype io, const void *h, const void *dout, void *dh, int batch, size_t half_elems,
                       int64_t h_batch_stride, int64_t dout_batch_stride, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_GATE, (double)batch * half_elems * esz(io) * 5.0);
     if (!h || !dout || !dh) return OSS_ERR_NULL;
     if (batch <= 0 || half_elems == 0) return OSS_ERR_SHAPE;
     return gelu_gate_bwd(io, h, dout, dh, batch, half_elems, h_batch_stride, dout_batch_stride, reinterpret_cast<hipStream_t>(stream));
 }
 
-int oss_conv3x3_thin_ok(oss_dtype io, int cin, int cout, int height, int width) { return conv3x3_thin_ok(io, cin, cout, height, width); }
+int oss_conv3x3_thin_ok(oss_dtype io, int cin, int cout, int height, int width) {
+    if (is_f32_split(io)) return 0;
+    return conv3x3_thin_ok(io, cin, cout, height, width);
+}
 int oss_conv3x3_thin_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cin, int cout,
                          int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
     if (!x || !weight || !y) return OSS_ERR_NULL;
     return conv3x3_thin_fwd(io, x, weight, bias, y, batch, cin, cout, height, width, xsb, xsc, ysb, ysc, reinterpret_cast<hipStream_t>(stream));
 }
 int oss_conv3x3_thin_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cin, int cout, int height,
                            int width, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
     if (!dy || !weight || !dx) return OSS_ERR_NULL;
     return conv3x3_thin_dgrad(io, dy, weight, dx, batch, cin, cout, height, width, gsb, gsc, dsb, dsc, reinterpret_cast<hipStream_t>(stream));
@@ -660,6 +716,7 @@ size_t oss_conv3x3_thin_wgrad_partial_floats(int batch, int cin, int cout) {
 }
 int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *dweight, float *dbias, float *partial, int batch, int cin,
                            int cout, int height, int width, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
     if (!x || !dy || !dweight || !partial) return OSS_ERR_NULL;
     return conv3x3_thin_wgrad(io, x, dy, dweight, dbias, partial, batch, cin, cout, height, width, xsb, xsc, gsb, gsc,
@@ -667,6 +724,7 @@ int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *d
 }
 
 int oss_image_metrics_ok(oss_dtype io, int channels, int height, int width, int crop_border, int flags) {
+    if (is_f32_split(io)) return 0;
     return image_metrics_ok(io, channels, height, width, crop_border, flags);
 }
 size_t oss_image_metrics_partial_doubles(int batch, int channels, int height, int width, int crop_border) {
@@ -675,6 +733,7 @@ size_t oss_image_metrics_partial_doubles(int batch, int channels, int height, in
 int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, double *partials, int batch, int channels, int height,
                       int width, int64_t asb, int64_t asc, int64_t ars, int64_t bsb, int64_t bsc, int64_t brs, int crop_border, int flags,
                       oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     if (!a || !b || !out || !partials) return OSS_ERR_NULL;
     return image_metrics(io, a, b, out, partials, batch, channels, height, width, asb, asc, ars, bsb, bsc, brs, crop_border, flags,
                          reinterpret_cast<hipStream_t>(stream));
@@ -785,6 +844,7 @@ int oss_adamw_ema_step(const oss_adam_chunk *chunks, int n_chunks, float *state,
 }
 
 int oss_merge4(oss_dtype io, const void *out, float *y, int batch, int D, int height, int width, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     fam_count(FAM_MERGE, (double)batch * D * height * width * (4.0 * esz(io) + 4.0));
     if (!out || !y) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0 || (long)batch * D > 65535) return OSS_ERR_SHAPE;
@@ -794,6 +854,7 @@ int oss_merge4(oss_dtype io, const void *out, float *y, int batch, int D, int he
 int oss_ln_nchw_fwd(oss_dtype xt, oss_dtype yt, const void *x, const float *weight, const float *bias, const void *gate,
                     void *y, float *mean, float *rstd, int batch, int channels, int pixels, int64_t xsb, int64_t xsc,
                     int64_t gsb, int64_t gsc, float eps, oss_stream_t stream) {
+    if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
     fam_count(FAM_LN, (double)batch * channels * pixels * (esz(xt) + esz(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
     if (!x || !weight || !y || !mean || !rstd) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
@@ -809,6 +870,7 @@ int oss_ln_nchw_fwd_pool_tiles(int channels, int pixels, int64_t xsb, int64_t xs
 int oss_ln_nchw_fwd_pool(oss_dtype xt, oss_dtype yt, const void *x, const float *weight, const float *bias, const void *gate, void *y,
                          float *mean, float *rstd, float *pool_part, int batch, int channels, int pixels, int64_t xsb, int64_t xsc,
                          int64_t gsb, int64_t gsc, float eps, oss_stream_t stream) {
+    if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
     fam_count(FAM_LN, (double)batch * channels * pixels * (esz(xt) + esz(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
     if (!x || !weight || !y || !mean || !rstd || !pool_part) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535 || channels > 4096) return OSS_ERR_SHAPE;
@@ -820,6 +882,7 @@ int oss_ln_nchw_bwd(oss_dtype xt, oss_dtype yt, const void *x, const float *weig
                     const void *dy, const float *mean, const float *rstd, void *dx, void *dgate, float *dweight,
                     float *dbias, float *partials, const void *skip_grad, int batch, int channels, int pixels, int64_t xsb,
                     int64_t xsc, int64_t gsb, int64_t gsc, int64_t dgate_batch_stride, oss_stream_t stream) {
+    if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
     fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * esz(xt) + esz(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
     if (!x || !weight || !dy || !mean || !rstd || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (gate && !dgate) return OSS_ERR_NULL;
@@ -834,6 +897,7 @@ int oss_ln_nchw_bwd_affine(oss_dtype xt, oss_dtype yt, const void *x, const floa
                            void *dgate, float *dweight, float *dbias, float *partials, const void *skip_grad, int batch,
                            int channels, int pixels, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc,
                            int64_t dgate_batch_stride, oss_stream_t stream) {
+    if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
     fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * esz(xt) + esz(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
     if (!x || !weight || !dy || !mean || !rstd || !dx || !dweight || !partials || !dy_add) return OSS_ERR_NULL;
     if (gate && !dgate) return OSS_ERR_NULL;
@@ -876,6 +940,7 @@ void oss_prof_reset(void) {
 
 int oss_prof_collect2(int which, int variant, oss_dtype io, double *total_ms, long long *launches, double *algorithmic_bytes,
                       double *own_bytes) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     const int rc = oss_prof_collect(which, variant, io, total_ms, launches, algorithmic_bytes);
     if (rc == OSS_OK && own_bytes) {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -885,6 +950,7 @@ int oss_prof_collect2(int which, int variant, oss_dtype io, double *total_ms, lo
 }
 
 int oss_prof_collect(int which, int variant, oss_dtype io, double *total_ms, long long *launches, double *algorithmic_bytes) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     if (which < 0 || which > 2 || variant < 0 || variant >= kProfVariants || (int)io < 0 || (int)io > 2) return OSS_ERR_SHAPE;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     ProfBucket &b = g_prof[which][variant][(int)io];
@@ -913,6 +979,8 @@ void oss_scan_set_segments(int fwd_segments, int bwd_segments) {
 int oss_scan_last_segments(int which) { return which == 0 ? g_last_fwd_segments.load() : g_last_bwd_segments.load(); }
 void oss_scan_set_carry_split(int split) { g_carry_split.store(split < 0 ? 0 : split); }
 int oss_scan_last_lane_states(void) { return g_last_bwd_lane_states.load(); }
+// fp32 product modes of the six GEMM-shaped entry points: bit 0 = exact (OSS_F32), bit 1 = split bf16 (OSS_F32_BF16X3)
+int oss_f32_matmul_modes(void) { return 1 | 2; }
 int oss_scan_features(void) { return (kBuildFusedDt ? OSS_FEATURE_FUSED_DT : 0) | (kBuildLaneStates ? OSS_FEATURE_LANE_STATES : 0); }
 
 // copy kernels of oss_hbm_copy.  Default (mode 2): one 16-byte element per lane and a grid as large as the buffer -- the

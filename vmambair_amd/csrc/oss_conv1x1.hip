@@ -1023,7 +1023,7 @@ static bool conv_wg_on() {
 void conv1x1_set_wg(int on) { g_conv_wg.store(on ? 1 : 0); }
 
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res) {
+            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res, int f32_split) {
     {
         const bool wt = (ws_m == 1 && ws_k == M), plain = (ws_k == 1 && ws_m == K);
         if ((wt || plain) && conv_wg_on() && conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res))
@@ -1040,7 +1040,7 @@ int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void
             break;
         default:   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
             return conv1x1_f32(reinterpret_cast<const float *>(x), w, bias, reinterpret_cast<float *>(y), B, M, K, P, xsb, xsk, ws_m, ws_k,
-                               s, reinterpret_cast<const float *>(res));
+                               s, reinterpret_cast<const float *>(res), f32_split);
     }
     return (int)hipGetLastError();
 }
@@ -1231,13 +1231,13 @@ void conv1x1_wgrad_set_span(int mult) { g_wgrad_span.store(mult < 1 ? 1 : (mult 
 
 int conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dw, float *part, int B, int M, int N, int P,
                   int64_t gsb, int64_t gsm, int64_t xsb, int64_t xsn, hipStream_t s, int G, int64_t gsg, int64_t xsg, int Mh,
-                  int64_t gs_hi, float *db) {
+                  int64_t gs_hi, float *db, int f32_split) {
     const int NB = N + (db ? 1 : 0);
     if (G < 1 || (size_t)B * G > 65535) return OSS_ERR_SHAPE;
     if (io == OSS_F32) {   // plain 1x1 weight gradient only (the projection products call rows_f32_wgrad themselves)
         if (G != 1 || (Mh > 0 && Mh != M)) return OSS_ERR_SHAPE;
         return rows_f32_wgrad(reinterpret_cast<const float *>(dy), reinterpret_cast<const float *>(x), dw, part, B, 1, 1, M, N, P, gsb, 0,
-                              gsm, xsb, 0, xsn, s, db);
+                              gsm, xsb, 0, xsn, s, db, f32_split);
     }
     if (Mh <= 0 || Mh > M) Mh = M;
     int slabs = conv1x1_wgrad_slabs(P);

@@ -43,6 +43,7 @@ __device__ __forceinline__ f32x4 quad_one_or_zero(const float *p, bool ok, bool 
     return *reinterpret_cast<GlobalQuadPtr>(a);
 }
 __device__ __forceinline__ float float_or_zero(const float *p, bool ok) { return *reinterpret_cast<GlobalFloatPtr>(addr_or_zero(p, ok)); }
+constexpr int kF32WgradSlab = 512;   // pixels per partial product of the weight-gradient kernels
 
 // ---- forward / input gradient -------------------------------------------------------------------------------------------------
 // Y[b][g][m][p] = sum_k W[g](m, k) X[b][g % GX][k][p] (+ bias[m]) (+ res[b][g][m][p]) (+ the old Y: accumulate)
@@ -56,11 +57,15 @@ struct F32Gemm {
     int M, K, P, G, GX, accumulate;
     int64_t xsb, xsg, xsk, wsg, wsm, wsk, ysb, ysg, ysm, rsb, rsg, rsm;
 };
+}  // namespace oss
+#include "oss_conv1x1_f32x3.h"   // the split-bf16 ("high") form of both products: its product loop, its weight-gradient kernel
+namespace oss {
 // SPLIT: a call with few tiles (a 1x1 convolution at batch 8 is 768 tiles for 1024 SIMDs) leaves every wave alone on its SIMD with
 // nothing to cover its loads -- measured 57 us per launch against ~5 us of matrix time (profiles/r04_ab_fp32_kernels.txt).  The
 // four waves of a 256-thread workgroup then take a quarter of K each (four times the waves, a quarter of the dependent
 // load -> MFMA rounds per wave) and wave 0 adds the four accumulator sets through LDS in wave order (deterministic).
-template <int MT, bool SPLIT>
+// X3: the products on split bf16 (oss_conv1x1_f32x3.h: OSS_F32_BF16X3) -- same tiles, same wave split, same epilogue, its own loop.
+template <int MT, bool SPLIT, bool X3 = false>
 __global__ void __launch_bounds__(SPLIT ? 256 : 64, 2)   // <= 256 registers (accumulators included)
 oss_conv1x1_f32_kernel(const F32Gemm a_) {
     const F32Gemm &a = a_;
@@ -70,8 +75,8 @@ oss_conv1x1_f32_kernel(const F32Gemm a_) {
     const int m0 = blockIdx.y * 32 * MT;
     const int b = blockIdx.z / a.G, g = blockIdx.z - b * a.G;
     const int M = a.M;
-    // this wave's channels [kbeg, K): an even number per wave, so that every k-step of two belongs to one wave
-    const int kq = SPLIT ? (((a.K + 3) / 4 + 1) & ~1) : a.K;
+    // this wave's channels [kbeg, K): an even number per wave, so that every k-step of two belongs to one wave (X3: whole rounds of 16)
+    const int kq = SPLIT ? (X3 ? 16 * ((a.K + 63) / 64) : (((a.K + 3) / 4 + 1) & ~1)) : a.K;
     const int kbeg = SPLIT ? wave * kq : 0, K = SPLIT ? min(a.K, kbeg + kq) : a.K;
     const bool pok = p0 < a.P;
     const float *xb = a.x + b * a.xsb + (g % a.GX) * a.xsg + (pok ? p0 : 0);
@@ -91,43 +96,47 @@ oss_conv1x1_f32_kernel(const F32Gemm a_) {
         mok[t] = m < M;
         wr[t] = wb + (int64_t)(mok[t] ? m : 0) * a.wsm;
     }
-    // Rounds of U k-steps: the loads of round r + 1 are issued BEFORE the MFMAs of round r (two register sets), so that a wave
-    // alone on its SIMD still keeps the matrix pipe busy across the ~1.5 us a load round trip takes under load (the first version
-    // issued a round's loads, waited, then ran its MFMAs: 57 us per 1x1 convolution against ~15 us of matrix time).
-    constexpr int U = MT == 1 ? 4 : 2;
-    auto load_round = [&](int k0, f32x4 (&xv)[U], float (&av)[U][MT]) {
+    if constexpr (X3) {
+        gemm_f32_bf16x3_loop<MT>(a, acc, xb, wr, mok, pok, kbeg, K, kg);
+    } else {
+        // Rounds of U k-steps: the loads of round r + 1 are issued BEFORE the MFMAs of round r (two register sets), so that a wave
+        // alone on its SIMD still keeps the matrix pipe busy across the ~1.5 us a load round trip takes under load (the first version
+        // issued a round's loads, waited, then ran its MFMAs: 57 us per 1x1 convolution against ~15 us of matrix time).
+        constexpr int U = MT == 1 ? 4 : 2;
+        auto load_round = [&](int k0, f32x4 (&xv)[U], float (&av)[U][MT]) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = k0 + 2 * u + kg;
-            const bool kok = k < K;
-            const int kc = kok ? k : 0;
-            xv[u] = quad_or_zero(xb + (int64_t)kc * a.xsk, kok && pok);
+            for (int u = 0; u < U; ++u) {
+                const int k = k0 + 2 * u + kg;
+                const bool kok = k < K;
+                const int kc = kok ? k : 0;
+                xv[u] = quad_or_zero(xb + (int64_t)kc * a.xsk, kok && pok);
 #pragma unroll
-            for (int t = 0; t < MT; ++t) av[u][t] = float_or_zero(wr[t] + (int64_t)kc * a.wsk, kok && mok[t]);
+                for (int t = 0; t < MT; ++t) av[u][t] = float_or_zero(wr[t] + (int64_t)kc * a.wsk, kok && mok[t]);
+            }
+        };
+        auto mfma_round = [&](const f32x4 (&xv)[U], const float (&av)[U][MT]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int t = 0; t < MT; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[t][q] = mfma_f32(av[u][t], xv[u][q], acc[t][q]);
+        };
+        f32x4 xa[U], xc[U];
+        float aa[U][MT], ac[U][MT];
+        // The prefetches are UNCONDITIONAL (a round past K reads the zero quad): behind a branch the compiler cannot count on them
+        // being in flight and falls back to waiting for (nearly) everything before the round's first MFMA (checked in the ISA).
+        load_round(kbeg, xa, aa);
+        for (int k0 = kbeg; k0 < K; k0 += 4 * U) {
+            load_round(k0 + 2 * U, xc, ac);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_round(xa, aa);
+            __builtin_amdgcn_sched_barrier(0);
+            load_round(k0 + 4 * U, xa, aa);
+            __builtin_amdgcn_sched_barrier(0);
+            if (k0 + 2 * U < K) mfma_round(xc, ac);
+            __builtin_amdgcn_sched_barrier(0);
         }
-    };
-    auto mfma_round = [&](const f32x4 (&xv)[U], const float (&av)[U][MT]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[t][q] = mfma_f32(av[u][t], xv[u][q], acc[t][q]);
-    };
-    f32x4 xa[U], xc[U];
-    float aa[U][MT], ac[U][MT];
-    // The prefetches are UNCONDITIONAL (a round past K reads the zero quad): behind a branch the compiler cannot count on them
-    // being in flight and falls back to waiting for (nearly) everything before the round's first MFMA (checked in the ISA).
-    load_round(kbeg, xa, aa);
-    for (int k0 = kbeg; k0 < K; k0 += 4 * U) {
-        load_round(k0 + 2 * U, xc, ac);
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_round(xa, aa);
-        __builtin_amdgcn_sched_barrier(0);
-        load_round(k0 + 4 * U, xa, aa);
-        __builtin_amdgcn_sched_barrier(0);
-        if (k0 + 2 * U < K) mfma_round(xc, ac);
-        __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (SPLIT) {
         extern __shared__ __attribute__((aligned(16))) float red[];   // [3 waves][MT * 16 quads][64 lanes][4]
@@ -219,23 +228,27 @@ static bool f32_aligned(std::initializer_list<const void *> ptrs, std::initializ
     return true;
 }
 
-int gemm_f32(const F32Gemm &a, int B, hipStream_t s) {
+// split != 0: fp32 tensors, products on split bf16 (OSS_F32_BF16X3) -- same shape rules, same tiles per launch form
+int gemm_f32(const F32Gemm &a, int B, hipStream_t s, int split) {
     if (a.M < 1 || a.K < 1 || a.P < 4 || a.P % 4 != 0 || a.G < 1 || a.GX < 1) return OSS_ERR_SHAPE;
     if (!f32_aligned({a.x, a.y, a.res}, {a.xsb, a.xsg, a.xsk, a.ysb, a.ysg, a.ysm, a.rsb, a.rsg, a.rsm})) return OSS_ERR_SHAPE;
     if (B <= 0 || (long)B * a.G > 65535) return OSS_ERR_SHAPE;
+    const bool x3 = split && kF32SplitGemm;
     const long px = (a.P + 127) / 128, bg = (long)B * a.G;
     const long waves64 = px * ((a.M + 63) / 64) * bg, waves32 = px * ((a.M + 31) / 32) * bg;
     if (waves64 >= 3072 && a.M > 32) {          // plenty of tiles: 64-row tiles, one wave each
         const dim3 grid(px, (a.M + 63) / 64, bg);
-        hipLaunchKernelGGL((oss_conv1x1_f32_kernel<2, false>), grid, dim3(64), 0, s, a);
-    } else if (waves32 >= 3072 || a.K < 32) {   // 32-row tiles, one wave each (a short K has nothing to split)
+        if (x3) hipLaunchKernelGGL((oss_conv1x1_f32_kernel<2, false, true>), grid, dim3(64), 0, s, a);
+        else    hipLaunchKernelGGL((oss_conv1x1_f32_kernel<2, false>), grid, dim3(64), 0, s, a);
+    } else if (waves32 >= 3072 || a.K < (x3 ? 64 : 32)) {   // 32-row tiles, one wave each (a short K has nothing to split: x3 works in rounds of 16)
         const dim3 grid(px, (a.M + 31) / 32, bg);
-        hipLaunchKernelGGL((oss_conv1x1_f32_kernel<1, false>), grid, dim3(64), 0, s, a);
+        if (x3) hipLaunchKernelGGL((oss_conv1x1_f32_kernel<1, false, true>), grid, dim3(64), 0, s, a);
+        else    hipLaunchKernelGGL((oss_conv1x1_f32_kernel<1, false>), grid, dim3(64), 0, s, a);
     } else {                                    // few tiles: four waves per tile, a quarter of K each
         const dim3 grid(px, (a.M + 31) / 32, bg);
         static LdsGate gate;
         const size_t smem = sizeof(float) * 3 * 16 * 64 * 4;
-        auto kern = oss_conv1x1_f32_kernel<1, true>;
+        auto kern = x3 ? oss_conv1x1_f32_kernel<1, true, true> : oss_conv1x1_f32_kernel<1, true>;
         if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
     }
@@ -243,13 +256,13 @@ int gemm_f32(const F32Gemm &a, int B, hipStream_t s) {
 }
 
 int conv1x1_f32(const float *x, const float *w, const float *bias, float *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                int64_t wsm, int64_t wsk, hipStream_t s, const float *res) {
+                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, int split) {
     F32Gemm a{};
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y;
     a.M = M; a.K = K; a.P = P; a.G = 1; a.GX = 1; a.accumulate = 0;
     a.xsb = xsb; a.xsg = 0; a.xsk = xsk; a.wsg = 0; a.wsm = wsm; a.wsk = wsk;
     a.ysb = (int64_t)M * P; a.ysg = 0; a.ysm = P; a.rsb = a.ysb; a.rsg = 0; a.rsm = P;
-    return gemm_f32(a, B, s);
+    return gemm_f32(a, B, s, split);
 }
 
 // x_proj / dt_proj of the four scan directions at fp32 I/O (MambaSISR6_arch.py:406-411) -- the products oss_proj_fwd / oss_proj_dgrad
@@ -262,29 +275,29 @@ int proj_f32_ok(int B, int D, int C, int R, int L, std::initializer_list<const v
 }
 // xdbl[b, k] (C rows) = Wx[k] (C x D) x2[b, k % 2] (D rows);  dts[b, k] (D rows) = Wdt[k] (D x R) xdbl[b, k][:R]
 int proj_fwd_f32(const float *x2, const float *Wx, const float *Wdt, float *xdbl, float *dts, int B, int D, int C, int R, int L,
-                 hipStream_t s) {
+                 hipStream_t s, int split) {
     const int64_t l = L;
     F32Gemm a{};
     a.x = x2; a.w = Wx; a.y = xdbl; a.M = C; a.K = D; a.P = L; a.G = 4; a.GX = 2;
     a.xsb = 2 * D * l; a.xsg = D * l; a.xsk = l; a.wsg = (int64_t)C * D; a.wsm = D; a.wsk = 1;
     a.ysb = 4 * C * l; a.ysg = C * l; a.ysm = l;
-    int e = gemm_f32(a, B, s);
+    int e = gemm_f32(a, B, s, split);
     if (e || !dts) return e;
     F32Gemm d{};
     d.x = xdbl; d.w = Wdt; d.y = dts; d.M = D; d.K = R; d.P = L; d.G = 4; d.GX = 4;
     d.xsb = 4 * C * l; d.xsg = C * l; d.xsk = l; d.wsg = (int64_t)D * R; d.wsm = R; d.wsk = 1;
     d.ysb = 4 * D * l; d.ysg = D * l; d.ysm = l;
-    return gemm_f32(d, B, s);
+    return gemm_f32(d, B, s, split);
 }
 // dxdbl[b, k][:R] = Wdt[k]^T ddts[b, k];  dx2[b, j] = Wx[j]^T dxdbl[b, j] + Wx[j + 2]^T dxdbl[b, j + 2] (+ du[b, j] + du[b, j + 2])
 int proj_dgrad_f32(const float *ddts, float *dxdbl, const float *du, const float *Wx, const float *Wdt, float *dx2, int B, int D, int C,
-                   int R, int L, hipStream_t s) {
+                   int R, int L, hipStream_t s, int split) {
     const int64_t l = L;
     F32Gemm t{};
     t.x = ddts; t.w = Wdt; t.y = dxdbl; t.M = R; t.K = D; t.P = L; t.G = 4; t.GX = 4;
     t.xsb = 4 * D * l; t.xsg = D * l; t.xsk = l; t.wsg = (int64_t)D * R; t.wsm = 1; t.wsk = R;
     t.ysb = 4 * C * l; t.ysg = C * l; t.ysm = l;
-    int e = gemm_f32(t, B, s);
+    int e = gemm_f32(t, B, s, split);
     if (e) return e;
     for (int kk = 0; kk < 2; ++kk) {   // directions j (kk = 0) and j + 2 (kk = 1) of flattening j, the second pass accumulates
         F32Gemm a{};
@@ -293,7 +306,7 @@ int proj_dgrad_f32(const float *ddts, float *dxdbl, const float *du, const float
         a.M = D; a.K = C; a.P = L; a.G = 2; a.GX = 2; a.accumulate = kk;
         a.xsb = 4 * C * l; a.xsg = C * l; a.xsk = l; a.wsg = (int64_t)C * D; a.wsm = 1; a.wsk = D;
         a.ysb = 2 * D * l; a.ysg = D * l; a.ysm = l; a.rsb = 4 * D * l; a.rsg = D * l; a.rsm = l;
-        e = gemm_f32(a, B, s);
+        e = gemm_f32(a, B, s, split);
         if (e) return e;
     }
     return 0;
@@ -303,7 +316,6 @@ int proj_dgrad_f32(const float *ddts, float *dxdbl, const float *du, const float
 // part[(b * slabs + slab)][g][m][n] = sum over the slab's pixels of A[b][g][m][p] Bm[b][g % GB][n][p]
 //   A row (b, g, m):  a + b * asb + g * asg + m * asm;   Bm row (b, g % GB, n):  bm + b * bsb + (g % GB) * bsg + n * bsn
 // one wave = a (32 TM) x (32 TN) tile of one (b, g, slab); grid (slabs, B * G, ceil(tiles / 4)), 256 threads (4 tiles).
-constexpr int kF32WgradSlab = 512;   // pixels per partial product
 template <int TM, int TN>
 __global__ void __launch_bounds__(256)
 oss_rows_f32_wgrad_kernel(const float *__restrict__ a, const float *__restrict__ bm, float *__restrict__ part, int M, int N, int P, int G,
@@ -431,20 +443,19 @@ int rows_f32_wgrad_ok(int M, int N, int P, const void *a, const void *bm, std::i
 }
 
 int rows_f32_wgrad(const float *a, const float *bm, float *out, float *part, int B, int G, int GB, int M, int N, int P, int64_t asb,
-                   int64_t asg, int64_t asm_, int64_t bsb, int64_t bsg, int64_t bsn, hipStream_t s, float *db) {
+                   int64_t asg, int64_t asm_, int64_t bsb, int64_t bsg, int64_t bsn, hipStream_t s, float *db, int split) {
     if (!rows_f32_wgrad_ok(M, N, P, a, bm, {asb, asg, asm_, bsb, bsg, bsn})) return OSS_ERR_SHAPE;
     if (B <= 0 || G <= 0 || GB <= 0 || (size_t)B * G > 65535 || (db && G != 1)) return OSS_ERR_SHAPE;
     const int NB = N + (db ? 1 : 0);
     const int slabs = rows_f32_wgrad_slabs(P);
     // 64 x 32 tiles; 32 x 32 when the wider tile would leave most SIMDs without a wave
     const int t21 = ((M + 63) / 64) * ((NB + 31) / 32), t11 = ((M + 31) / 32) * ((NB + 31) / 32);
-    if ((long)t21 * slabs * B * G >= 1024 && M > 32) {
-        const dim3 grid(slabs, B * G, (t21 + 3) / 4);
-        hipLaunchKernelGGL((oss_rows_f32_wgrad_kernel<2, 1>), grid, dim3(256), 0, s, a, bm, part, M, N, P, G, GB, asb, asg, asm_, bsb, bsg, bsn, NB);
-    } else {
-        const dim3 grid(slabs, B * G, (t11 + 3) / 4);
-        hipLaunchKernelGGL((oss_rows_f32_wgrad_kernel<1, 1>), grid, dim3(256), 0, s, a, bm, part, M, N, P, G, GB, asb, asg, asm_, bsb, bsg, bsn, NB);
-    }
+    // (split != 0: the same tiles and the same partial layout on the split-bf16 kernel of oss_conv1x1_f32x3.h)
+    const bool wide = (long)t21 * slabs * B * G >= 1024 && M > 32;
+    const dim3 grid(slabs, B * G, ((wide ? t21 : t11) + 3) / 4);
+    auto kern = split && kF32SplitWgrad ? (wide ? oss_rows_f32_wgrad_bf16x3_kernel<2, 1> : oss_rows_f32_wgrad_bf16x3_kernel<1, 1>)
+                                        : (wide ? oss_rows_f32_wgrad_kernel<2, 1> : oss_rows_f32_wgrad_kernel<1, 1>);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a, bm, part, M, N, P, G, GB, asb, asg, asm_, bsb, bsg, bsn, NB);
     const size_t nw = (size_t)G * M * N, pvec = nw + (db ? M : 0);
     if (defer_finish())
         defer_sum(part, slabs * B, pvec, pvec, out, nw, db);

@@ -678,6 +678,7 @@ int dwconv3x3(oss_dtype io, const void *x, const float *w, const float *bias, vo
         case OSS_F32: return dwconv_launch<float>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
         case OSS_F16: return dwconv_launch<f16_t>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
         case OSS_BF16: return dwconv_launch<bf16_t>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
+        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
     }
     return OSS_ERR_SHAPE;
 }
@@ -861,6 +862,7 @@ int dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, floa
         case OSS_F32: return wgrad_launch<float>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
         case OSS_F16: return wgrad_launch<f16_t>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
         case OSS_BF16: return wgrad_launch<bf16_t>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
+        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
     }
     return OSS_ERR_SHAPE;
 }

@@ -102,17 +102,17 @@ int dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *w, const 
 int dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, float *db, float *part, int B, int C, int H,
                     int W, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, hipStream_t s, const void *pre = nullptr,
                     void *dpre = nullptr);
-// fp32 I/O on v_mfma_f32_32x32x2_f32 (oss_conv1x1_f32.hip)
+// fp32 I/O on v_mfma_f32_32x32x2_f32 (oss_conv1x1_f32.hip); split != 0: the products on split bf16 (OSS_F32_BF16X3, oss_conv1x1_f32x3.h)
 int conv1x1_f32(const float *x, const float *w, const float *bias, float *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                int64_t wsm, int64_t wsk, hipStream_t s, const float *res);
+                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, int split = 0);
 int proj_f32_ok(int B, int D, int C, int R, int L, std::initializer_list<const void *> ptrs);
 int proj_fwd_f32(const float *x2, const float *Wx, const float *Wdt, float *xdbl, float *dts, int B, int D, int C, int R, int L,
-                 hipStream_t s);
+                 hipStream_t s, int split = 0);
 int proj_dgrad_f32(const float *ddts, float *dxdbl, const float *du, const float *Wx, const float *Wdt, float *dx2, int B, int D, int C,
-                   int R, int L, hipStream_t s);
+                   int R, int L, hipStream_t s, int split = 0);
 size_t rows_f32_wgrad_partial_floats(int B, int G, int M, int N, int P);
 int rows_f32_wgrad(const float *a, const float *bm, float *out, float *part, int B, int G, int GB, int M, int N, int P, int64_t asb,
-                   int64_t asg, int64_t asm_, int64_t bsb, int64_t bsg, int64_t bsn, hipStream_t s, float *db = nullptr);
+                   int64_t asg, int64_t asm_, int64_t bsb, int64_t bsg, int64_t bsn, hipStream_t s, float *db = nullptr, int split = 0);
 // thin dense 3x3 convolutions (oss_conv3x3_thin.hip): <= 4 channels in or out
 int conv3x3_thin_ok(oss_dtype io, int Cin, int Cout, int H, int W);
 int conv3x3_thin_fwd(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int Cin, int Cout, int H, int W,
@@ -148,17 +148,17 @@ int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, c
 int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
                int64_t xsk, int wt, hipStream_t s, const void *res = nullptr);
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res = nullptr);
+            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res = nullptr, int f32_split = 0);
 int conv1x1_wgrad_slabs(int P);
 void conv1x1_wgrad_set_tile(int mode);
 void conv1x1_wgrad_set_span(int mult);
 int conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dw, float *part, int B, int M, int N, int P,
                   int64_t gsb, int64_t gsm, int64_t xsb, int64_t xsn, hipStream_t s, int G = 1, int64_t gsg = 0, int64_t xsg = 0,
-                  int Mh = 0, int64_t gs_hi = 0, float *db = nullptr);
+                  int Mh = 0, int64_t gs_hi = 0, float *db = nullptr, int f32_split = 0);
 int proj_fwd(oss_dtype io, const void *x2, const float *Wx, const float *Wdt, void *xdbl, void *dts, int B, int D, int C, int R,
-             int L, hipStream_t s);
+             int L, hipStream_t s, int f32_split = 0);
 int proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, const float *Wx, const float *Wdt, void *dx2, int B,
-               int D, int C, int R, int L, hipStream_t s);
+               int D, int C, int R, int L, hipStream_t s, int f32_split = 0);
 void proj_force_valu(int on);
 bool proj_mfma_ok(oss_dtype io, int B, int D, int C, int R, int L);
 int cross_scan2(oss_dtype it, oss_dtype ot, const void *x, void *x2, int B, int D, int H, int W, int64_t xsb, int64_t xsc,

@@ -796,35 +796,37 @@ bool proj_mfma_ok(oss_dtype io, int B, int D, int C, int R, int L) {
 }
 
 int proj_fwd(oss_dtype io, const void *x2, const float *Wx, const float *Wdt, void *xdbl, void *dts, int B, int D, int C, int R,
-             int L, hipStream_t s) {
+             int L, hipStream_t s, int f32_split) {
     if (!dts && !proj_mfma_ok(io, B, D, C, R, L)) return OSS_ERR_NULL;   // dts may be omitted on the matrix-core path only
     if (proj_mfma_ok(io, B, D, C, R, L))
         return io == OSS_BF16 ? proj_fwd_mfma_t<bf16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s)
                               : proj_fwd_mfma_t<f16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
     if (io == OSS_F32 && dts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {x2, xdbl, dts}))   // (round 4) fp32 matrix cores
         return proj_fwd_f32(reinterpret_cast<const float *>(x2), Wx, Wdt, reinterpret_cast<float *>(xdbl), reinterpret_cast<float *>(dts),
-                            B, D, C, R, L, s);
+                            B, D, C, R, L, s, f32_split);
     switch (io) {
         case OSS_F32: return proj_fwd_t<float>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
         case OSS_F16: return proj_fwd_t<f16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
         case OSS_BF16: return proj_fwd_t<bf16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
+        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
     }
     return OSS_ERR_SHAPE;
 }
 
 int proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, const float *Wx, const float *Wdt, void *dx2, int B,
-               int D, int C, int R, int L, hipStream_t s) {
+               int D, int C, int R, int L, hipStream_t s, int f32_split) {
     if (!ddts && !proj_mfma_ok(io, B, D, C, R, L)) return OSS_ERR_NULL;
     if (proj_mfma_ok(io, B, D, C, R, L))
         return io == OSS_BF16 ? proj_dgrad_mfma_t<bf16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s)
                               : proj_dgrad_mfma_t<f16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
     if (io == OSS_F32 && ddts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {ddts, dxdbl, du, dx2}))
         return proj_dgrad_f32(reinterpret_cast<const float *>(ddts), reinterpret_cast<float *>(dxdbl), reinterpret_cast<const float *>(du),
-                              Wx, Wdt, reinterpret_cast<float *>(dx2), B, D, C, R, L, s);
+                              Wx, Wdt, reinterpret_cast<float *>(dx2), B, D, C, R, L, s, f32_split);
     switch (io) {
         case OSS_F32: return proj_dgrad_t<float>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
         case OSS_F16: return proj_dgrad_t<f16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
         case OSS_BF16: return proj_dgrad_t<bf16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
+        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
     }
     return OSS_ERR_SHAPE;
 }

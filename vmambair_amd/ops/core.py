@@ -10,7 +10,7 @@ from typing import List, Optional
 
 import torch
 
-from .. import _capi
+from .. import _capi, _precision
 from ._common import (_DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_operands, _keep_views, _recorded_before, _planes, _ptr)  # noqa: F401
 from . import scan as _scan
 from .scan import merge4, selective_scan_bwd, selective_scan_fwd
@@ -101,7 +101,8 @@ def _proj_weights(x_proj_weight, dt_projs_weight):
 
 def proj_fwd(x2: torch.Tensor, x_proj_weight: torch.Tensor, dt_projs_weight: torch.Tensor, want_dts: bool = True) -> List[torch.Tensor]:
     """x2 (B, 2, D, L) -> [xdbl (B, 4, R + 2N, L), dts (B, 4 D, L)] (MambaSISR6_arch.py:406-411, omni form).
-    ``want_dts=False`` (fused-delta form): the dt projection is left to the scan kernels, ``dts`` comes back empty."""
+    ``want_dts=False`` (fused-delta form): the dt projection is left to the scan kernels, ``dts`` comes back empty.
+    float32 tensors follow ``vmambair_amd.set_float32_matmul_precision`` (read when the op runs, like ``proj_dgrad`` / ``proj_wgrad``)."""
     B, _, D, L = x2.shape
     Cc, R = x_proj_weight.shape[1], dt_projs_weight.shape[2]
     wx, wdt = _proj_weights(x_proj_weight, dt_projs_weight)
@@ -110,7 +111,7 @@ def proj_fwd(x2: torch.Tensor, x_proj_weight: torch.Tensor, dt_projs_weight: tor
     dts = torch.empty((B, 4 * D, L) if want_dts else (0,), dtype=x2.dtype, device=x2.device)
     if x2.numel():
         with torch.cuda.device(x2.device):
-            _capi.check(_capi.load().oss_proj_fwd(_DT[x2.dtype], x2.data_ptr(), wx.data_ptr(), wdt.data_ptr(), xdbl.data_ptr(),
+            _capi.check(_capi.load().oss_proj_fwd(_precision.io_code(x2.dtype), x2.data_ptr(), wx.data_ptr(), wdt.data_ptr(), xdbl.data_ptr(),
                                                   dts.data_ptr() if want_dts else None, B, D, Cc, R, L,
                                                   torch.cuda.current_stream().cuda_stream), "oss_proj_fwd")
     return [xdbl, dts]
@@ -128,7 +129,7 @@ def proj_dgrad(ddts: Optional[torch.Tensor], dxdbl: torch.Tensor, du: Optional[t
     dx2 = torch.empty((B, 2, D, L), dtype=dxdbl.dtype, device=dxdbl.device)
     if dx2.numel():
         with torch.cuda.device(dxdbl.device):
-            _capi.check(_capi.load().oss_proj_dgrad(_DT[dxdbl.dtype], _ptr(ddts), dxdbl.data_ptr(), _ptr(du), wx.data_ptr(),
+            _capi.check(_capi.load().oss_proj_dgrad(_precision.io_code(dxdbl.dtype), _ptr(ddts), dxdbl.data_ptr(), _ptr(du), wx.data_ptr(),
                                                     wdt.data_ptr(), dx2.data_ptr(), B, D, Cc, R, L,
                                                     torch.cuda.current_stream().cuda_stream), "oss_proj_dgrad")
     return dx2
@@ -155,7 +156,7 @@ def proj_wgrad(x2: torch.Tensor, xdbl: torch.Tensor, dxdbl: torch.Tensor, ddts: 
             dwdt = torch.empty((4, D, R), dtype=torch.float32, device=dev) if ddts is not None else None
             part = torch.empty((max(1, lib.oss_proj_wgrad_partial_floats(B, D, Cc, R, L)),), dtype=torch.float32, device=dev)
             rec0 = _recorded_before()
-            _capi.check(lib.oss_proj_wgrad(_DT[x2.dtype], x2.data_ptr(), xdbl.data_ptr(), dxdbl.data_ptr(), _ptr(ddts),
+            _capi.check(lib.oss_proj_wgrad(_precision.io_code(x2.dtype), x2.data_ptr(), xdbl.data_ptr(), dxdbl.data_ptr(), _ptr(ddts),
                                            dwx.data_ptr(), _ptr(dwdt), part.data_ptr(), B, D, Cc, R, L,
                                            torch.cuda.current_stream().cuda_stream), "oss_proj_wgrad")
             _keep(part, dwx, dwdt)

@@ -10,14 +10,16 @@ from typing import List, Optional
 
 import torch
 
-from .. import _capi
+from .. import _capi, _precision
 from ._common import (_keep_operands, _recorded_before,
                       _DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_views, _planes, _ptr)  # noqa: F401
 
 
 def conv1x1_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``F.conv2d(x, weight, bias) [+ residual]`` for a (Cout, Cin, 1, 1) weight; x bf16/fp16 (B, Cin, H, W)."""
+    """``F.conv2d(x, weight, bias) [+ residual]`` for a (Cout, Cin, 1, 1) weight; x bf16/fp16 (B, Cin, H, W).
+    float32 x: exact fp32 products, or split-bf16 ones under ``vmambair_amd.set_float32_matmul_precision("high")`` -- the mode is
+    read here, when the op runs (a captured hipGraph keeps the mode it was captured under)."""
     _check(x.is_cuda and x.dim() == 4 and x.dtype in _DT, "conv1x1: x must be bf16 / fp16 / fp32 on the GPU")
     B, Cin, H, W = x.shape
     Cout = weight.shape[0]
@@ -38,7 +40,7 @@ def conv1x1_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
         return y
     lib = _capi.load()
     with torch.cuda.device(x.device):
-        _capi.check(lib.oss_conv1x1_fwd(_DT[x.dtype], x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(residual), y.data_ptr(), B, Cout, Cin,
+        _capi.check(lib.oss_conv1x1_fwd(_precision.io_code(x.dtype), x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(residual), y.data_ptr(), B, Cout, Cin,
                                         H * W, x.stride(0), x.stride(1), torch.cuda.current_stream().cuda_stream), "oss_conv1x1_fwd")
     return y
 
@@ -66,7 +68,7 @@ def conv1x1_bwd(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, has_bia
             db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if has_bias else None
             part = torch.empty(int(lib.oss_conv1x1_wgrad_partial_floats(B, Cout, Cin, P)), dtype=torch.float32, device=x.device)
             rec0 = _recorded_before()
-            _capi.check(lib.oss_conv1x1_wgrad(_DT[x.dtype], dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), part.data_ptr(), B,
+            _capi.check(lib.oss_conv1x1_wgrad(_precision.io_code(x.dtype), dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), part.data_ptr(), B,
                                               Cout, Cin, P, dy.stride(0), dy.stride(1), x.stride(0), x.stride(1),
                                               torch.cuda.current_stream().cuda_stream), "oss_conv1x1_wgrad")
             _keep(part, dw, db)
@@ -74,7 +76,7 @@ def conv1x1_bwd(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, has_bia
         if f32 and CONV1X1_F32_WGRAD_ONLY:
             dx = torch.nn.functional.conv_transpose2d(dy, weight.detach().float())
         else:
-            _capi.check(lib.oss_conv1x1_dgrad(_DT[x.dtype], dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, Cout, Cin, P,
+            _capi.check(lib.oss_conv1x1_dgrad(_precision.io_code(x.dtype), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, Cout, Cin, P,
                                               dy.stride(0), dy.stride(1), torch.cuda.current_stream().cuda_stream), "oss_conv1x1_dgrad")
     return [dx, dw.view(Cout, Cin, 1, 1), db if db is not None else x.new_empty(0, dtype=torch.float32)]
 
