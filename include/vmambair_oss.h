@@ -24,6 +24,13 @@
  * asynchronous on `stream`, never synchronise the host, and are re-entrant.
  * Return value: 0 on success, a negative OSS_ERR_* for a rejected argument, or a positive
  * hipError_t if the launch failed.
+ *
+ * The ctypes binding (vmambair_amd/_capi.py) is READ from this file by vmambair_amd/_cheader.py, which is no C parser, so
+ * everything between the extern "C" braces keeps to this subset (anything else is a load-time error there, never skipped):
+ *   #define OSS_NAME <int> | (<int>);   typedef enum { NAME = <int>, ... } name;   typedef void *name;
+ *   typedef struct { <type> [*]field, [*]field; ... } name;   -- scalar, pointer and earlier-struct fields; no arrays, bit-fields, unions
+ *   <ret> oss_name(<type> [*[*]][name], ...);   -- also (void); no function pointers, arrays or varargs
+ *   types: int, int64_t, size_t, float, double, long long, the typedefs above, and pointers to anything
  */
 #ifndef VMAMBAIR_OSS_H
 #define VMAMBAIR_OSS_H
@@ -704,8 +711,9 @@ int oss_f32_matmul_modes(void);
  * every change of a struct or of an entry point's argument list (8: the value OSS_F32_BF16X3 of oss_dtype and
  * oss_f32_matmul_modes(); no struct changed); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
- * in this tree (vmambair_amd/_capi.py, csrc_host/oss_torch_host.cpp through vmambair_amd/_host.py) compares both with its
- * own compile-time values when it loads and refuses to run on a mismatch. */
+ * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
+ * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
+ * number below is the only place to bump. */
 #define OSS_ABI_VERSION 8
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);

@@ -1,5 +1,6 @@
-"""The C-ABI library: loads without a GPU, exports every symbol include/vmambair_oss.h declares,
-and the ctypes structures have the layout the header gives them.  No compute calls here."""
+"""The C-ABI library: loads without a GPU, exports every symbol include/vmambair_oss.h declares, and the ctypes binding that
+vmambair_amd/_cheader.py reads out of that header has the prototypes and the struct layout a C compiler gives them.  No compute
+calls here."""
 import ctypes
 import os
 import re
@@ -9,16 +10,17 @@ import pytest
 import torch
 
 import vmambair_amd
-from vmambair_amd import _build, _capi
+from vmambair_amd import _build, _capi, _cheader
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "vmambair_oss.h")
+HEADER = _build.HEADER
+
+
+def _stripped_header():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(oss_[a-z_0-9]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(oss_[a-z_0-9]+)\s*\(", _stripped_header())))
 
 
 def test_library_is_built_and_loads():
@@ -33,41 +35,139 @@ def test_library_is_built_and_loads():
 def test_every_declared_symbol_is_exported():
     declared = _declared_functions()
     assert declared == sorted(_capi.SYMBOLS)
+    assert declared == sorted(_cheader.read(HEADER).prototypes), "the header reader dropped or invented a prototype"
     lib = ctypes.CDLL(_build.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
 
 
+def test_prototypes_are_complete():
+    """after load() every declared function carries a full prototype; the parameter count comes from a plain comma count of the
+    header's text, not from the reader"""
+    lib = _capi.load()
+    found = re.findall(r"\b(oss_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", _stripped_header())
+    assert sorted(n for n, _ in found) == _declared_functions()
+    for name, args in found:
+        fn = getattr(lib, name)
+        n_params = 0 if args.strip() == "void" else args.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == n_params, name
+        assert fn.restype in (ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p, None), name
+
+
 def test_struct_layout_matches_header():
-    """Compile a tiny C probe against the header and compare sizeof/offsetof with ctypes."""
-    probe = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "vmambair_oss.h"
-int main(void) {
-  printf("%zu %zu ", offsetof(oss_scan_fwd_params, workspace), offsetof(oss_scan_fwd_params, workspace_bytes));
-  printf("%zu %zu %zu %zu %zu %zu ", offsetof(oss_scan_fwd_params, dt_weight), offsetof(oss_scan_fwd_params, dt_rank),
-         offsetof(oss_scan_fwd_params, dt_rank_stride), offsetof(oss_scan_bwd_params, ddt), offsetof(oss_scan_bwd_params, ddt_weight),
-         offsetof(oss_scan_bwd_params, ddt_rank_stride));
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(oss_scan_fwd_params), offsetof(oss_scan_fwd_params, u_batch_stride),
-         offsetof(oss_scan_fwd_params, u), offsetof(oss_scan_fwd_params, x), sizeof(oss_scan_bwd_params),
-         offsetof(oss_scan_bwd_params, dout_batch_stride), offsetof(oss_scan_bwd_params, dout),
-         offsetof(oss_scan_bwd_params, workspace_bytes), offsetof(oss_scan_bwd_params, dBC_group_stride),
-         sizeof(oss_chan_params), offsetof(oss_chan_params, pooled), offsetof(oss_chan_params, zt), offsetof(oss_chan_params, c));
-  return 0; }'''
+    """Compile a C probe against the header that prints sizeof and every field's offsetof of all five structs, generated from
+    the parsed field lists, and compare with the ctypes classes."""
+    structs = _cheader.read(HEADER).structs
+    assert list(structs) == ["oss_scan_fwd_params", "oss_scan_bwd_params", "oss_chan_params", "oss_sum_chunk", "oss_adam_chunk"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vmambair_oss.h"', 'int main(void) {']
+    want = []
+    for name, cls in structs.items():
+        lines.append(f'  printf("%zu\\n", sizeof({name}));')
+        want.append(ctypes.sizeof(cls))
+        for field, _ in cls._fields_:
+            lines.append(f'  printf("%zu\\n", offsetof({name}, {field}));')
+            want.append(getattr(cls, field).offset)
+    lines.append('  return 0; }')
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         c = os.path.join(td, "probe.c")
-        open(c, "w").write(probe)
+        open(c, "w").write("\n".join(lines))
         exe = os.path.join(td, "probe")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
+        subprocess.check_call(["gcc", "-I", os.path.dirname(HEADER), c, "-o", exe])
         got = [int(v) for v in subprocess.check_output([exe]).split()]
-    F, B, Ch = _capi.ScanFwdParams, _capi.ScanBwdParams, _capi.ChanParams
-    want = [F.workspace.offset, F.workspace_bytes.offset, F.dt_weight.offset, F.dt_rank.offset, F.dt_rank_stride.offset, B.ddt.offset, B.ddt_weight.offset, B.ddt_rank_stride.offset,
-            ctypes.sizeof(F), F.u_batch_stride.offset, F.u.offset, F.x.offset, ctypes.sizeof(B),
-            B.dout_batch_stride.offset, B.dout.offset, B.workspace_bytes.offset, B.dBC_group_stride.offset,
-            ctypes.sizeof(Ch), Ch.pooled.offset, Ch.zt.offset, Ch.c.offset]
-    assert got == want
+    assert len(want) > 100 and got == want
+    # the classes the package hands out are that layout
+    for name, cls in (("oss_scan_fwd_params", _capi.ScanFwdParams), ("oss_scan_bwd_params", _capi.ScanBwdParams),
+                      ("oss_chan_params", _capi.ChanParams), ("oss_adam_chunk", _capi.AdamChunk)):
+        assert [(f, getattr(cls, f).offset) for f, _ in cls._fields_] == [(f, getattr(structs[name], f).offset) for f, _ in structs[name]._fields_]
+        assert ctypes.sizeof(cls) == ctypes.sizeof(structs[name])
+    assert _capi.SUM_CHUNK_BYTES == ctypes.sizeof(structs["oss_sum_chunk"]) == 40
+    assert _capi.ScanBwdParams.f.offset == 0 and _capi.ScanBwdParams._fields_[0][1] is _capi.ScanFwdParams
+
+
+def test_every_error_code_has_a_message():
+    constants = _cheader.read(HEADER).constants
+    codes = {n: v for n, v in constants.items() if n.startswith("OSS_ERR_")}
+    assert len(codes) >= 4 and constants["OSS_OK"] == 0
+    for name, value in codes.items():
+        assert value < 0 and _capi.ERRORS[value].startswith(name + ":"), name
+    assert _capi.ABI_VERSION == constants["OSS_ABI_VERSION"] and _capi.ADAM_CHUNK == constants["OSS_ADAM_CHUNK"] == 2048
+    assert (_capi.OSS_F32, _capi.OSS_F16, _capi.OSS_BF16, _capi.OSS_F32_BF16X3) == (0, 1, 2, 3)
+    assert (_capi.METRIC_QUANTISE, _capi.METRIC_Y, _capi.METRIC_REPLICATE) == (1, 2, 4)
+    assert (_capi.FEATURE_FUSED_DT, _capi.FEATURE_LANE_STATES) == (1, 2)
+
+
+_SNIPPET = """
+/* a header in the subset */
+#ifndef GUARD_H
+#define GUARD_H
+#include <stdint.h>
+extern "C" {
+#define X (-4)
+#define OSS_Y 7     /* trailing comment */
+typedef enum { OSS_A = 0, OSS_B = 5 } oss_dtype;
+typedef void *oss_stream_t;
+typedef struct {
+    int n, m;
+    const float *a, *b;   /* the star belongs to the declarator */
+    int64_t stride;
+    float scale;
+} oss_inner_params;
+typedef struct {
+    oss_inner_params f;
+    void *out;
+    size_t bytes;
+} oss_outer_params;
+typedef struct { void *p; int n, reserved_; } oss_row;
+int oss_last(int which /* 0 fwd, 1 bwd */);
+const char *oss_version(void);
+void oss_reset(void);
+size_t oss_wrapped(oss_dtype io, const oss_outer_params *p,
+                   int64_t stride, const oss_row *rows,
+                   float eps, oss_stream_t stream);
+int oss_names(int i, const char **name, double *sum, long long *calls, double x, long long);
+}
+#endif
+"""
+
+
+def test_reader_on_synthetic_snippets():
+    C = ctypes
+    h = _cheader.parse(_SNIPPET)
+    assert h.constants == {"X": -4, "OSS_Y": 7, "OSS_A": 0, "OSS_B": 5}
+    inner, outer, row = (h.structs[n] for n in ("oss_inner_params", "oss_outer_params", "oss_row"))
+    assert list(h.structs) == ["oss_inner_params", "oss_outer_params", "oss_row"]
+    assert inner._fields_ == [("n", C.c_int), ("m", C.c_int), ("a", C.c_void_p), ("b", C.c_void_p), ("stride", C.c_int64),
+                              ("scale", C.c_float)]
+    assert outer._fields_ == [("f", inner), ("out", C.c_void_p), ("bytes", C.c_size_t)]
+    assert C.sizeof(inner) == 40 and outer.out.offset == 40 and C.sizeof(outer) == 56 and C.sizeof(row) == 16
+    assert h.prototypes == {
+        "oss_last": (C.c_int, [C.c_int]),
+        "oss_version": (C.c_char_p, []),
+        "oss_reset": (None, []),
+        "oss_wrapped": (C.c_size_t, [C.c_int, C.POINTER(outer), C.c_int64, C.c_void_p, C.c_float, C.c_void_p]),
+        "oss_names": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_longlong]),
+    }
+    assert list(h.prototypes) == ["oss_last", "oss_version", "oss_reset", "oss_wrapped", "oss_names"]
+
+
+@pytest.mark.parametrize("bad, names", [
+    ("int oss_f(unsigned short x);", "unsigned short"),                         # a type outside the table
+    ("typedef struct { unsigned short x; } oss_s;", "unsigned short"),
+    ("int oss_f(int n, void (*callback)(int));", "callback"),                   # function pointer
+    ("int oss_f(int n);\nsize_t oss_g(void);\nint oss_f(int n);", "oss_f"),     # duplicate prototype
+    ("#define OSS_A 1\ntypedef enum { OSS_A = 1 } oss_e;", "OSS_A"),            # duplicate constant
+    ("typedef struct { int a[4]; } oss_s;", "a[4]"),                            # array field
+    ("typedef union { int a; float b; } oss_u;", "union"),                      # a typedef it cannot read
+    ("int oss_f(int n, ...);", "..."),
+    ("int oss_f(int n)", "oss_f"),                                              # no terminating semicolon
+    ("#define OSS_A (1 << 3)", "1 << 3"),
+    ("static int oss_f(int n);", "static"),
+])
+def test_reader_refuses_what_it_cannot_read(bad, names):
+    with pytest.raises(RuntimeError) as e:
+        _cheader.parse(bad)
+    assert names in str(e.value)
 
 
 def test_workspace_query_is_pure():

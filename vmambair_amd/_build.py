@@ -16,6 +16,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libvmambair_oss.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]
+#: the public header: the C ABI, and the text vmambair_amd/_capi.py derives its ctypes binding from (_cheader.py)
+HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "vmambair_oss.h"))
 
 
 #: the files the scan kernels are compiled from: their hash is the library's oss_scan_build_id()
@@ -116,7 +118,7 @@ def host_stale() -> bool:
     if not os.path.exists(HOST_LIB):
         return True
     t = os.path.getmtime(HOST_LIB)
-    deps = [HOST_SRC, os.path.join(HERE, "..", "include", "vmambair_oss.h")]
+    deps = [HOST_SRC, HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
