@@ -648,6 +648,31 @@ int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *d
                            int cout, int height, int width, int64_t x_batch_stride, int64_t x_channel_stride, int64_t dy_batch_stride,
                            int64_t dy_channel_stride, oss_stream_t stream);
 
+/* The GEMM-shaped dense 3x3 convolutions (stride 1, zero padding 1, NCHW) of the UNet skeleton on the matrix cores: Downsample
+ * conv(n -> n/2), Upsample conv(n -> 2n) and the x4 tail's two conv(n -> 4n) (vmambair_amd/archs.py).  16-bit I/O, fp32 master
+ * weights (cout, cin, 3, 3) and bias narrowed to the I/O type where they are loaded, fp32 accumulation, one rounding after the bias.
+ * oss_conv3x3_dense_ok is a pure host query: 1 for bf16 / fp16, cin % 16 == 0 (16 .. 16384), 5 <= cout <= 16384 and
+ * 1 <= height, width <= 32768 (odd widths included), else 0; a call on an accepted shape with 1 <= batch <= 65535 never fails to
+ * launch, anything else returns OSS_ERR_SHAPE.  Batch and channel strides (elements) are free, planes are contiguous.  With 16-byte
+ * aligned pointers, strides that are multiples of 8 and width % 8 == 0 the loaders use 16-byte accesses, element-wise ones otherwise.
+ *   fwd:   y = conv(x) + bias
+ *   dgrad: dx = the transposed convolution of dy (the forward kernel with the weights read transposed and mirrored)
+ *   wgrad: dweight (cout, cin, 3, 3) through `partial` (oss_conv3x3_dense_wgrad_partial_floats floats, no init): one partial vector of
+ *          9 cin cout floats per (image, row band) -- at most batch * height vectors, about 512 workgroups' worth for large planes --
+ *          added in that order by the deferred finishing launch (oss_set_defer_finish) or right away.  With dbias != NULL also
+ *          dbias = sum dy, by a launch of its own that sums in fp64 and rounds once.  No atomics: reruns are bit-identical. */
+int oss_conv3x3_dense_ok(oss_dtype io, int cin, int cout, int height, int width);
+int oss_conv3x3_dense_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cin, int cout,
+                          int height, int width, int64_t x_batch_stride, int64_t x_channel_stride, int64_t y_batch_stride,
+                          int64_t y_channel_stride, oss_stream_t stream);
+int oss_conv3x3_dense_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cin, int cout, int height,
+                            int width, int64_t dy_batch_stride, int64_t dy_channel_stride, int64_t dx_batch_stride,
+                            int64_t dx_channel_stride, oss_stream_t stream);
+size_t oss_conv3x3_dense_wgrad_partial_floats(int batch, int cin, int cout, int height, int width);
+int oss_conv3x3_dense_wgrad(oss_dtype io, const void *x, const void *dy, float *dweight, float *dbias, float *partial, int batch, int cin,
+                            int cout, int height, int width, int64_t x_batch_stride, int64_t x_channel_stride, int64_t dy_batch_stride,
+                            int64_t dy_channel_stride, oss_stream_t stream);
+
 /* The reference's validation metrics of a batch of image pairs, on the device, in one call: the mean squared error behind
  * calculate_psnr (Deraining/basicsr/metrics/psnr_ssim.py:9-63) and the mean SSIM of _ssim (psnr_ssim.py:66-99; Deraining/Deraining/
  * utils.py:31-78) or _ssim_cly (psnr_ssim.py:184-222), with 11 x 11 Gaussian window (sigma 1.5), C1 = (0.01 * 255)^2,

@@ -37,7 +37,7 @@ class Downsample(nn.Module):
         self.body = nn.Sequential(_conv3(n_feat, n_feat // 2, False), nn.PixelUnshuffle(2))
 
     def forward(self, x):
-        return self.body(x)
+        return self.body[1](conv3x3(x, self.body[0]))   # conv3x3 ends in body[0](x) unless the dense kernels are switched on
 
 
 class Upsample(nn.Module):
@@ -46,7 +46,7 @@ class Upsample(nn.Module):
         self.body = nn.Sequential(_conv3(n_feat, n_feat * 2, False), nn.PixelShuffle(2))
 
     def forward(self, x):
-        return self.body(x)
+        return self.body[1](conv3x3(x, self.body[0]))
 
 
 def _x4_tail(n_feat: int, out_channels: int) -> nn.Sequential:
@@ -196,7 +196,10 @@ class MambaSISR6(_OSSUNet):
     def forward(self, inp_img):
         # tail = Sequential(upsampler, conv_last): the last layer (2 dim -> out_channels at the output resolution) on the in-tree
         # thin-convolution kernels; parameter names (tail.0.*, tail.1.*) are the reference's
-        return conv3x3(self.tail[0](self.body(inp_img)), self.tail[1]) + F.interpolate(inp_img, scale_factor=self.scale, mode="nearest")
+        up, last = self.tail
+        t = up[1](conv3x3(self.body(inp_img), up[0]))
+        t = up[3](conv3x3(t, up[2]))
+        return conv3x3(t, last) + F.interpolate(inp_img, scale_factor=self.scale, mode="nearest")
 
 
 class MambaRealSR11(MambaSISR6):

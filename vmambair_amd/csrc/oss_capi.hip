@@ -723,6 +723,43 @@ int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *d
                               reinterpret_cast<hipStream_t>(stream));
 }
 
+int oss_conv3x3_dense_ok(oss_dtype io, int cin, int cout, int height, int width) {
+    if (is_f32_split(io)) return 0;
+    return conv3x3_dense_ok(io, cin, cout, height, width);
+}
+// algorithmic bytes of one call: both activation tensors once, the fp32 weights once
+static double dense_bytes(oss_dtype io, int batch, int cin, int cout, int height, int width) {
+    return (double)batch * height * width * esz(io) * ((double)cin + cout) + 36.0 * cin * cout;
+}
+int oss_conv3x3_dense_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cin, int cout,
+                          int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    fam_count(FAM_CONV3X3, dense_bytes(io, batch, cin, cout, height, width));
+    if (!x || !weight || !y) return OSS_ERR_NULL;
+    return conv3x3_dense_fwd(io, x, weight, bias, y, batch, cin, cout, height, width, xsb, xsc, ysb, ysc, reinterpret_cast<hipStream_t>(stream));
+}
+int oss_conv3x3_dense_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cin, int cout, int height,
+                            int width, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    fam_count(FAM_CONV3X3, dense_bytes(io, batch, cin, cout, height, width));
+    if (!dy || !weight || !dx) return OSS_ERR_NULL;
+    return conv3x3_dense_dgrad(io, dy, weight, dx, batch, cin, cout, height, width, gsb, gsc, dsb, dsc, reinterpret_cast<hipStream_t>(stream));
+}
+size_t oss_conv3x3_dense_wgrad_partial_floats(int batch, int cin, int cout, int height, int width) {
+    if (batch <= 0 || batch > 65535 || cin < 16 || cin % 16 != 0 || cin > 16384 || cout < 5 || cout > 16384 || height < 1 ||
+        height > 32768 || width < 1 || width > 32768)
+        return 0;
+    return conv3x3_dense_wgrad_partial_floats(batch, cin, cout, height, width);
+}
+int oss_conv3x3_dense_wgrad(oss_dtype io, const void *x, const void *dy, float *dweight, float *dbias, float *partial, int batch, int cin,
+                            int cout, int height, int width, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    fam_count(FAM_CONV3X3, dense_bytes(io, batch, cin, cout, height, width));
+    if (!x || !dy || !dweight || !partial) return OSS_ERR_NULL;
+    return conv3x3_dense_wgrad(io, x, dy, dweight, dbias, partial, batch, cin, cout, height, width, xsb, xsc, gsb, gsc,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
 int oss_image_metrics_ok(oss_dtype io, int channels, int height, int width, int crop_border, int flags) {
     if (is_f32_split(io)) return 0;
     return image_metrics_ok(io, channels, height, width, crop_border, flags);

@@ -122,6 +122,15 @@ int conv3x3_thin_dgrad(oss_dtype io, const void *dy, const float *w, void *dx, i
 size_t conv3x3_thin_wgrad_partial_floats(int B, int Cin, int Cout);
 int conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, float *db, float *part, int B, int Cin, int Cout, int H,
                        int W, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, hipStream_t s);
+// GEMM-shaped dense 3x3 convolutions on the matrix cores (oss_conv3x3_dense.hip): Cin % 16 == 0, Cout >= 5
+int conv3x3_dense_ok(oss_dtype io, int Cin, int Cout, int H, int W);
+int conv3x3_dense_fwd(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int Cin, int Cout, int H, int W,
+                      int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, hipStream_t s);
+int conv3x3_dense_dgrad(oss_dtype io, const void *dy, const float *w, void *dx, int B, int Cin, int Cout, int H, int W, int64_t gsb,
+                        int64_t gsc, int64_t dsb, int64_t dsc, hipStream_t s);
+size_t conv3x3_dense_wgrad_partial_floats(int B, int Cin, int Cout, int H, int W);
+int conv3x3_dense_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, float *db, float *part, int B, int Cin, int Cout, int H,
+                        int W, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, hipStream_t s);
 int ln_nchw_fwd(oss_dtype xt, oss_dtype yt, const void *x, const float *w, const float *bias, const void *gate, void *y,
                 float *mean, float *rstd, int B, int C, int P, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, float eps,
                 hipStream_t s, float *pool_part = nullptr);

@@ -6,7 +6,8 @@ One module per operator family (round 1 had a single 1 000-line ``ops.py``):
   ``core``      the spatial branch of SS2D_1 as one node (flattenings + projections + scan + merge)
   ``channel``   the channel branch + gate as one node
   ``pointwise`` in_conv / out_conv / project_in / project_out (1x1 convolutions) on the matrix cores
-  ``conv3x3``   dense 3x3 convolutions with <= 4 channels on one side (patch_embed, the tail's last layer)
+  ``conv3x3``   dense 3x3 convolutions with <= 4 channels on one side (patch_embed, the tail's last layer); opt-in MFMA kernels
+                for the GEMM-shaped ones of the skeleton (Downsample, Upsample, the x4 tail)
   ``dwconv``    depth-wise 3x3 (+ silu)          ``layernorm``  NCHW LayerNorm (+ gate)          ``ffn``  gelu gate of the EFFN
   ``metrics``   validation PSNR + SSIM of a batch of image pairs in one call (mean squared error, mean SSIM; fp64 on the device)
   ``_common``   dtype table, checks, deferred finishing, weight-gradient side stream
@@ -30,6 +31,7 @@ from .core import (ConvCoreFn, SS2DCoreFn, conv_core_ok, core_supported, cross_m
 from .dwconv import (DWConv3x3Fn, DWGateFn, dwconv3x3, dwconv3x3_bwd, dwconv3x3_fwd, dwconv3x3_gelu_gate,  # noqa: F401
                      dwconv3x3_silu_bwd, dwconv3x3_silu_flat2_bwd, dwconv3x3_silu_flat2_fwd, dwconv3x3_silu_fwd, dwgate_bwd, dwgate_fwd, flat2_ok)
 from .conv3x3 import ThinConv3x3Fn, conv3x3_thin_bwd, conv3x3_thin_fwd  # noqa: F401
+from .conv3x3 import DenseConv3x3Fn, conv3x3_dense_bwd, conv3x3_dense_fwd, dense_ok, set_dense  # noqa: F401
 from .conv3x3 import conv3x3 as conv3x3_layer  # noqa: F401
 from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gate, gelu_gate_bwd, gelu_gate_fwd  # noqa: F401
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401

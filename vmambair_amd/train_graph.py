@@ -97,6 +97,9 @@ class GraphedTrainStep:
                     continue  # the MFMA 1x1 kernels read the fp32 masters and narrow them in their loader
                 if dense_conv and m.kernel_size == (3, 3) and min(m.in_channels, m.out_channels) <= 4 and _ops.conv3x3.THIN_IMPL:
                     continue  # patch_embed / the tail's last layer: the thin-convolution kernels read the fp32 masters (ops/conv3x3.py)
+                if dense_conv and m.kernel_size == (3, 3) and _ops.conv3x3.DENSE_IMPL and m.in_channels % 16 == 0 and m.out_channels >= 5 \
+                        and m.stride == (1, 1) and m.padding == (1, 1) and m.dilation == (1, 1) and m.padding_mode == "zeros":
+                    continue  # the skeleton's GEMM-shaped layers on the dense MFMA kernels: they read the fp32 masters too
                 # x_proj_weight / dt_projs_weight: the fused spatial core (SS2DCoreFn) reads the fp32 masters
                 fused_proj = getattr(m, "fused_core", False) and getattr(m, "omni", False)
                 if dense_conv or (leaf in ("x_proj_weight", "dt_projs_weight") and not fused_proj):
