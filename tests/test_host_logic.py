@@ -585,3 +585,20 @@ def test_scan_tune_tuple_maps_to_the_struct_encoding():
     assert _tune_fields((13, 1, None, "bf16")) == (14, 1, 0, 2)
     assert _tune_fields((None, None, None)) == (0, 0, 0, 0)
     assert _tune_fields((-1, -1, 0, None)) == (0, 0, 0, 0)
+
+
+def test_csrc_has_no_compile_time_switches():
+    """One build: the only preprocessor conditional under ``vmambair_amd/csrc/`` is the ``OSS_SCAN_BUILD_ID`` default of
+    ``oss_capi.hip``, and neither the kernels nor the package's Python name an experiment (``OSS_EXP_*``) or feature (``OSS_WITHOUT_*``)
+    macro.  A timing-only form of a kernel lives on a branch and is A-B'd from a second worktree (``VMAMBAIR_LIB``)."""
+    import glob
+    import os
+    import re
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vmambair_amd")
+    csrc = sorted(f for f in glob.glob(os.path.join(pkg, "csrc", "**"), recursive=True) if os.path.isfile(f))
+    assert len(csrc) > 20
+    conditionals = [(os.path.basename(f), ln.strip()) for f in csrc for ln in open(f).read().splitlines()
+                    if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", ln)]
+    assert conditionals == [("oss_capi.hip", "#ifndef OSS_SCAN_BUILD_ID")]
+    for f in csrc + sorted(glob.glob(os.path.join(pkg, "*.py"))):
+        assert not re.search(r"OSS_EXP_|OSS_WITHOUT_", open(f).read()), f

@@ -23,18 +23,12 @@ HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "vmambair_oss.h"))
 #: the files the scan kernels are compiled from: their hash is the library's oss_scan_build_id()
 SCAN_FILES = ("oss_scan_fwd.hip", "oss_scan_bwd.hip", "oss_scan_bwd_v2.h", "oss_device.h")
 
-def feature_flags():
-    """(rounds 4-5: VMAMBAIR_BUILD_FEATURES compiled the fused-delta / lane-state scan forms in; since round 6 every library has
-    them -- csrc/oss_host.h: kBuildFusedDt / kBuildLaneStates -- and there is ONE build)"""
-    return []
-
 
 def scan_build_id() -> str:
     import hashlib
     h = hashlib.sha256()
     for f in SCAN_FILES:
         h.update(open(os.path.join(CSRC, f), "rb").read())
-    h.update(" ".join(feature_flags()).encode())
     return h.hexdigest()[:12]
 
 
@@ -87,13 +81,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
     idfile = os.path.join(OBJ_DIR, "scan_build_id.txt")
     if not (os.path.exists(idfile) and open(idfile).read() == bid):   # the id is compiled into oss_capi.o
         open(idfile, "w").write(bid)
-        # ... and the build features are compiled into the scan translation units
+        # ... and the scan translation units are rebuilt with it, so that the id always names the objects in the library
         for name in ("oss_capi.hip", *[f for f in SCAN_FILES if f.endswith(".hip")]):
             if os.path.join(CSRC, name) not in todo:
                 todo.append(os.path.join(CSRC, name))
 
     def compile_one(src):
-        cmd = [hipcc, *FLAGS, *feature_flags(), f'-DOSS_SCAN_BUILD_ID="{bid}"', "-c", src, "-o", _obj(src) + ".tmp"]
+        cmd = [hipcc, *FLAGS, f'-DOSS_SCAN_BUILD_ID="{bid}"', "-c", src, "-o", _obj(src) + ".tmp"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -44,7 +44,7 @@ _lib = None
 
 
 def lib_path() -> str:
-    # VMAMBAIR_LIB: timing experiments only (tools/build_experiment.sh)
+    # VMAMBAIR_LIB: a library built from another checkout (its own _build.build()), for A-B timing of two revisions
     return os.environ.get("VMAMBAIR_LIB") or _build.LIB_PATH
 
 
@@ -79,15 +79,15 @@ def load():
 
 
 def has_feature(bit: int) -> bool:
-    """opt-in build features of the loaded library (include/vmambair_oss.h: oss_scan_features)"""
+    """scan forms the loaded library reports (include/vmambair_oss.h: oss_scan_features)"""
     return bool(load().oss_scan_features() & bit)
 
 
 def require_feature(bit: int, what: str) -> None:
     if not has_feature(bit):
         name = {FEATURE_FUSED_DT: "fused_dt", FEATURE_LANE_STATES: "lane_states"}[bit]
-        raise RuntimeError(f"{what}: {lib_path()} was built without the scan form '{name}' "
-                           f"(-DOSS_WITHOUT_... in csrc/oss_host.h; the shipped build has both)")
+        raise RuntimeError(f"{what}: {lib_path()} does not report the scan form '{name}' "
+                           f"(oss_scan_features; every library built from this tree has both)")
 
 
 def check(rc: int, what: str) -> None:

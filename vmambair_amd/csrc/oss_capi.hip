@@ -245,7 +245,7 @@ static double bwd_own_bytes(const oss_scan_bwd_params &q, int s) {
 
 static int check_fwd(const oss_scan_fwd_params *p) {
     if (!p || !p->u || !p->delta || !p->A || !p->B || !p->C) return OSS_ERR_NULL;
-    if (p->dt_weight && (!kBuildFusedDt || p->dt_rank < 1 || p->dt_rank > kMaxDtRank)) return OSS_ERR_SHAPE;
+    if (p->dt_weight && (p->dt_rank < 1 || p->dt_rank > kMaxDtRank)) return OSS_ERR_SHAPE;
     if (p->batch < 0 || p->dim <= 0 || p->seqlen < 0 || p->dstate <= 0 || p->n_groups <= 0) return OSS_ERR_SHAPE;
     if (p->dim % p->n_groups != 0) return OSS_ERR_SHAPE;  // selective_scan.cpp:190
     if (p->dstate > OSS_MAX_DSTATE) return OSS_ERR_DSTATE;  // selective_scan.cpp:191
@@ -311,7 +311,7 @@ size_t oss_scan_bwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, 
 }
 
 size_t oss_scan_lane_state_floats(int batch, int dim, int seqlen, int dstate) {
-    if (!kBuildLaneStates || batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0) return 0;
+    if (batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0) return 0;
     return (size_t)batch * dim * dstate * lane_state_stride(seqlen);
 }
 
@@ -542,7 +542,7 @@ int oss_proj_rows_optional_ok(oss_dtype io, int batch, int D, int C, int R, int 
 }
 int oss_scan_fused_dt_ok(oss_dtype io, int batch, int D, int C, int R, int dstate, int seqlen) {
     if (is_f32_split(io)) return 0;
-    return kBuildFusedDt && proj_mfma_ok(io, batch, D, C, R, seqlen) && R >= 1 && R <= kMaxDtRank && dstate <= 64 && seqlen >= 512;
+    return proj_mfma_ok(io, batch, D, C, R, seqlen) && R >= 1 && R <= kMaxDtRank && dstate <= 64 && seqlen >= 512;
 }
 int oss_conv1x1_wg(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cout, int cin,
                    int pixels, int64_t xsb, int64_t xsc, int transposed_weight, oss_stream_t stream) {
@@ -1018,7 +1018,7 @@ void oss_scan_set_carry_split(int split) { g_carry_split.store(split < 0 ? 0 : s
 int oss_scan_last_lane_states(void) { return g_last_bwd_lane_states.load(); }
 // fp32 product modes of the six GEMM-shaped entry points: bit 0 = exact (OSS_F32), bit 1 = split bf16 (OSS_F32_BF16X3)
 int oss_f32_matmul_modes(void) { return 1 | 2; }
-int oss_scan_features(void) { return (kBuildFusedDt ? OSS_FEATURE_FUSED_DT : 0) | (kBuildLaneStates ? OSS_FEATURE_LANE_STATES : 0); }
+int oss_scan_features(void) { return OSS_FEATURE_FUSED_DT | OSS_FEATURE_LANE_STATES; }
 
 // copy kernels of oss_hbm_copy.  Default (mode 2): one 16-byte element per lane and a grid as large as the buffer -- the
 // dispatcher streams short workgroups faster than any loop keeps loads in flight: 6.12 TB/s on 1 GiB, against 5.58 for

@@ -61,13 +61,6 @@ __global__ void __launch_bounds__(NT)
 oss_chan_fwd_kernel(oss_chan_params p) {
     extern __shared__ float sm[];
     const int b = blockIdx.x, tid = threadIdx.x, L = p.L, dc = p.dc, Cc = p.Cc, Rc = p.Rc;
-#ifdef OSS_EXP_CHAN_TIMING  // (timing experiments only: tools/build_experiment.sh) phase stamps in shader cycles -> zt[0..7]
-    long long ts_[8]; int ns_ = 0;
-#define OSS_STAMP() do { ts_[ns_++] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OSS_STAMP() do { } while (0)
-#endif
-    OSS_STAMP();
     const bool lift = p.cin_w != nullptr;
     float *seq = sm;                 // [dc][L]
     float *ybuf = seq + dc * L;      // [2 dc][L]
@@ -131,7 +124,6 @@ oss_chan_fwd_kernel(oss_chan_params p) {
         for (int i = 0; i < dc; ++i) seq[i * L + l] = lift ? __builtin_fmaf(p.cin_w[i], pl, p.cin_b[i]) : pl;
     }
     __syncthreads();
-    OSS_STAMP();
     float *zg = p.zt + (size_t)b * 2 * L * Cc;  // [k][l][c]
     float *dg = p.dts + (size_t)b * 2 * dc * L;
     float *zb, *db, *dlsF = nullptr;   // dlsF [2 dc][L]: softplus(dts + bias), computed once per (row, l) for the 16 state lanes
@@ -161,7 +153,6 @@ oss_chan_fwd_kernel(oss_chan_params p) {
         }
     }
     __syncthreads();
-    OSS_STAMP();
     // dts[row][l] = sum_r Wdtc[row][r] z[k][l][r]: NT / (2 dc) threads per row, the row's first 8 weights in registers
     {
         const int nrow = 2 * dc, tpr = NT / nrow;      // dc <= 4: >= 32 threads per row
@@ -190,7 +181,6 @@ oss_chan_fwd_kernel(oss_chan_params p) {
         }
     }
     __syncthreads();
-    OSS_STAMP();
     // ---- the two channel-direction scans, time across the lanes (round 3) -------------------------------------------------
     // wave = (direction k, group of NPG states); lane p of a 128-step chunk owns steps 2p, 2p + 1 of the direction's walk.
     // Per (row, state): the two local steps, one 64-lane scan of the recurrence monoid (oss_device.h: segment_scan), the chunk
@@ -277,7 +267,6 @@ oss_chan_fwd_kernel(oss_chan_params p) {
     for (int idx = tid; idx < 2 * dc * L; idx += NT)   // y = D u + the groups' sums over their states, in group order
         ybuf[idx] = ((ypart[idx] + ypart[2 * dc * L + idx]) + ypart[2 * 2 * dc * L + idx]) + ypart[3 * 2 * dc * L + idx];
     __syncthreads();
-    OSS_STAMP();
     float part = 0.f;
     for (int l = tid; l < L; l += NT) {
         float s = lift ? p.cout_b[0] : 0.f;
@@ -295,13 +284,6 @@ oss_chan_fwd_kernel(oss_chan_params p) {
         p.c[(size_t)b * L + l] = __builtin_fmaf((ycs[l] - mu) * rstd, p.cn_w[l], p.cn_b[l]);
     }
     if (tid == 0) { p.stat[b * 2] = mu; p.stat[b * 2 + 1] = rstd; }
-#ifdef OSS_EXP_CHAN_TIMING
-    OSS_STAMP();
-    __syncthreads();
-    if (b == 0 && tid == 0)
-        for (int q = 1; q < ns_; ++q) zg[q - 1] = (float)(ts_[q] - ts_[q - 1]);
-#endif
-#undef OSS_STAMP
 }
 
 // gradient slots of one image in gpart (B, NP); oss_chan_grad_floats() = NP
@@ -320,13 +302,6 @@ oss_chan_bwd_kernel(oss_chan_params p, const float *__restrict__ gc /*(B, L): gr
                     int stage_zdt /* the dt columns of z fit in LDS next to everything else */) {
     extern __shared__ float sm[];
     const int b = blockIdx.x, tid = threadIdx.x, L = p.L, dc = p.dc, Cc = p.Cc, Rc = p.Rc;
-#ifdef OSS_EXP_CHAN_TIMING  // phase stamps -> gpart[b = 0][0..] (the other images write zeros there)
-    long long ts_[10]; int ns_ = 0;
-#define OSS_STAMP() do { ts_[ns_++] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OSS_STAMP() do { } while (0)
-#endif
-    OSS_STAMP();
     const bool lift = p.cin_w != nullptr;
     const ChanSlots sl(L, dc, Rc, Cc);
     // the scan phase's layout (see there): wave = (direction, group of NPG states), lane = two steps of a 128-step chunk.  The
@@ -407,7 +382,6 @@ oss_chan_bwd_kernel(oss_chan_params p, const float *__restrict__ gc /*(B, L): gr
         dys[l] = rstd * (g - m1 - xh * m2);
     }
     __syncthreads();
-    OSS_STAMP();
     const float *yb = p.y + (size_t)b * 2 * dc * L;
     const float *zb = p.zt + (size_t)b * 2 * L * Cc;
     // ---- both reverse recurrences, time across the lanes (round 3; the forward kernel's layout walked backwards) -----------
@@ -561,7 +535,6 @@ oss_chan_bwd_kernel(oss_chan_params p, const float *__restrict__ gc /*(B, L): gr
         }
     }
     __syncthreads();
-    OSS_STAMP();
     // dt rows of dz
     {   // a thread keeps the dc weights of its column (k, r) in registers and walks l
         const int ncol = 2 * Rc;
@@ -596,13 +569,11 @@ oss_chan_bwd_kernel(oss_chan_params p, const float *__restrict__ gc /*(B, L): gr
         dsq[idx] = s;
     }
     __syncthreads();
-    OSS_STAMP();
     for (int l = tid; l < L; l += NT) {
         float s = 0.f;
         for (int i = 0; i < dc; ++i) s = lift ? __builtin_fmaf(p.cin_w[i], dsq[i * L + l], s) : s + dsq[i * L + l];
         dpool[(size_t)b * L + l] = s;
     }
-    OSS_STAMP();
     // parameter gradients that are sums over l: one output per thread
     const int n_wdtc = 2 * dc * Rc, n_wxc = 2 * Cc * dc;
     for (int o = tid; o < n_wdtc + n_wxc + 2 * dc; o += NT) {
@@ -631,13 +602,6 @@ oss_chan_bwd_kernel(oss_chan_params p, const float *__restrict__ gc /*(B, L): gr
             gp[sl.cinw + q] = s;
         }
     }
-#ifdef OSS_EXP_CHAN_TIMING
-    OSS_STAMP();
-    __syncthreads();
-    if (tid == 0)
-        for (int q = 1; q < ns_; ++q) gp[q - 1] = b == 0 ? (float)(ts_[q] - ts_[q - 1]) : 0.f;
-#endif
-#undef OSS_STAMP
 }
 
 // gsum[j] = sum_b gpart[b][j] in batch order

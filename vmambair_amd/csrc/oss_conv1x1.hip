@@ -117,11 +117,7 @@ oss_conv1x1_reuse_kernel(const T *__restrict__ x, const float *__restrict__ w, c
         for (int e = 0; e < 8; ++e) {
             const int k = ks * 16 + kg * 8 + e;
             const bool kok = k < K;
-#ifdef OSS_EXP_CONV_NOLOAD  // (timing experiments only: tools/build_experiment.sh)
-            const short xv = (short)(lane * 3 + k);
-#else
             const short xv = (short)xb[(kok ? k : K - 1) * xsk].v;
-#endif
             bfr[ks][e] = (pok && kok) ? xv : (short)0;
         }
     }
@@ -143,12 +139,8 @@ oss_conv1x1_reuse_kernel(const T *__restrict__ x, const float *__restrict__ w, c
                 if constexpr (!WT) {
                     const bool kok = k0 + 8 <= K;
                     const float *wp = w + mc * K + (kok ? k0 : 0);
-#ifdef OSS_EXP_CONV_NOW
-                    const f32x4 w0 = {(float)lane, 1.f, 2.f, (float)mt}, w1 = {3.f, (float)ks, 4.f, 5.f};
-#else
                     const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wp);
                     const f32x4 w1 = *reinterpret_cast<const f32x4 *>(wp + 4);
-#endif
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         af[e] = (mok && kok) ? to_bits<T>(w0[e]) : (short)0;
@@ -169,11 +161,7 @@ oss_conv1x1_reuse_kernel(const T *__restrict__ x, const float *__restrict__ w, c
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-#ifdef OSS_EXP_CONV_NOSTORE
-            if (row < M && pok && acc[r] == 123456.789f) {
-#else
             if (row < M && pok) {
-#endif
                 float v = acc[r] + (bias ? bias[row] : 0.f);
                 if (res) v += to_f32(res[(size_t)b * M * P + (size_t)row * P + p]);  // fused residual: y = W x + bias + res
                 yb[(size_t)row * P + p] = from_f32<T>(v);
@@ -192,11 +180,7 @@ __device__ __forceinline__ s16x8 load_wfrag(const float *__restrict__ w, int mro
     if constexpr (!WT && WVEC) {
         const bool kok = k0 + 8 <= K;
         const float *wp = w + mc * K + (kok ? k0 : 0);
-#ifdef OSS_EXP_HALF_W   // TIMING ONLY (wrong results): half of the weight bytes -- what 16-bit weight copies would cost to load
-        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wp), w1 = w0;
-#else
         const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wp), w1 = *reinterpret_cast<const f32x4 *>(wp + 4);
-#endif
         const s16x8 f = cvt8<T>(w0, w1);
         return (mok && kok) ? f : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
     } else {
@@ -206,12 +190,7 @@ __device__ __forceinline__ s16x8 load_wfrag(const float *__restrict__ w, int mro
             const int k = k0 + e;
             const bool kok = k < K;
             const int kc = kok ? k : K - 1;
-#ifdef OSS_EXP_HALF_W
-            const int kh = kc & ~1;
-            const float w1 = WT ? w[kh * M + mc] : w[mc * K + kh];
-#else
             const float w1 = WT ? w[kc * M + mc] : w[mc * K + kc];
-#endif
             wv[e] = (mok && kok) ? w1 : 0.f;
         }
         return cvt8<T>(f32x4{wv[0], wv[1], wv[2], wv[3]}, f32x4{wv[4], wv[5], wv[6], wv[7]});
@@ -264,11 +243,6 @@ struct WRaw { f32x4 lo[KS], hi[KS]; };
 // issue the loads of row `mrow`'s fragments (addresses clamped into the matrix: no condition on any load)
 template <int KS, bool WT, bool WVEC>
 __device__ __forceinline__ void wraw_issue(WRaw<KS> &r, const float *__restrict__ w, int mrow, int M, int K, int kg) {
-#ifdef OSS_EXP_CONV_NOW   // timing experiment: weight fragments without memory traffic
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) { r.lo[ks] = f32x4{1.f, 2.f, (float)mrow, (float)kg}; r.hi[ks] = r.lo[ks]; }
-    return;
-#endif
     const int mc = mrow < M ? mrow : 0;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -312,8 +286,8 @@ __device__ __forceinline__ void wraw_narrow(const WRaw<KS> &r, s16x8 (&af)[KS], 
 
 // Forward weights (W(m, k) = w[m * K + k], K % 8 == 0) through wave-private LDS.  The MFMA fragment of a lane is 8 consecutive
 // k of ITS OWN row: loaded straight from memory, one 16-byte load instruction touches 32 rows = 64 cache lines and the
-// texture addresser spends a cycle on each (the weight loads were 6 of the 18.6 us of in_conv at d = 96 -- experiment build
-// CONV_NOW, profiles/r02_conv1x1_pipeline.txt).  A row tile is ONE contiguous block of 32 K floats: lane l fetches the 16-byte
+// texture addresser spends a cycle on each (the weight loads were 6 of the 18.6 us of in_conv at d = 96 -- measured with a
+// since-removed experiment build, profiles/r02_conv1x1_pipeline.txt).  A row tile is ONE contiguous block of 32 K floats: lane l fetches the 16-byte
 // chunks l, l + 64, ... (fully coalesced), narrows them and parks them as [32][16 KS + 8] T (padded rows: conflict-free
 // 16-byte reads); the fragments are read back from there.  No barrier: LDS operations of one wave execute in order.
 template <int KS>
@@ -512,11 +486,7 @@ oss_conv1x1_pairw_kernel(const T *__restrict__ x, const float *__restrict__ w, c
         const int mcl = min(m0 + m4, M - 4);                   // (M % 4 == 0: a chunk is inside the matrix or wholly outside)
         f32x4 q[NI];
 #pragma unroll
-#ifdef OSS_EXP_HALF_W
-        for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(w + (size_t)min(kr + 32 * (i & ~1), K - 1) * M + mcl);
-#else
         for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(w + (size_t)min(kr + 32 * i, K - 1) * M + mcl);
-#endif
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int k = kr + 32 * i;
@@ -534,11 +504,7 @@ oss_conv1x1_pairw_kernel(const T *__restrict__ x, const float *__restrict__ w, c
         const float *base = w + (size_t)m0 * K;
         f32x4 q[NI];
 #pragma unroll
-#ifdef OSS_EXP_HALF_W
-        for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(base + min(4 * ((i & ~1) * 256 + tid), lim));
-#else
         for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(base + min(4 * (i * 256 + tid), lim));
-#endif
         int r = (4 * tid) / K, k = (4 * tid) - r * K;
         const int sr = 1024 / K, sk = 1024 - sr * K;
 #pragma unroll
@@ -698,7 +664,6 @@ wgrad_body(const T *__restrict__ dy, const T *__restrict__ x, float *__restrict_
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
         int pk = pbeg;
-#ifndef OSS_EXP_WGRAD_DIRECT
         for (; aligned && pend - pk >= kWgradSlab; pk += kWgradSlab) {   // full kWgradSlab pieces of the span, one after the other
             // A full slab, operands through LDS.  The MFMA fragment of a lane is 8 consecutive pixels of ITS OWN row (row =
             // lane & 31): loaded straight from memory, one 16-byte load instruction touches 32 rows -- 64 separate cache
@@ -759,32 +724,6 @@ wgrad_body(const T *__restrict__ dy, const T *__restrict__ x, float *__restrict_
             }
             __builtin_amdgcn_wave_barrier();   // the next piece's LDS writes stay behind this piece's reads
         }
-#else
-        if (aligned && pend - pk == kWgradSlab) {
-            // (timing experiment) a full slab: ALL its operand loads (2 x 16 bytes per k-step and lane) are issued before the first MFMA.
-            // A k-step is one MFMA (64 cycles) but a load is a ~1 us round trip: walked 64 pixels at a time (8 loads,
-            // wait, 4 MFMAs) the kernel was a chain of 8 round trips at 1.5 waves per SIMD.
-            constexpr int IT = kWgradSlab / 16;
-            u32x4 qa[IT], qb[IT];
-#pragma unroll
-            for (int u = 0; u < IT; ++u) {
-#ifdef OSS_EXP_WGRAD_NOLOAD   // timing experiment: operands without memory traffic
-                qa[u] = u32x4{(uint32_t)lane, (uint32_t)u, 1u, 2u};
-                qb[u] = u32x4{(uint32_t)lane, (uint32_t)u, 3u, 4u};
-#else
-                qa[u] = *reinterpret_cast<const u32x4 *>(ga + pk + u * 16 + kg * 8);
-                qb[u] = *reinterpret_cast<const u32x4 *>(xa + pk + u * 16 + kg * 8);
-#endif
-            }
-#pragma unroll
-            for (int u = 0; u < IT; ++u) {
-                const s16x8 af = mok ? __builtin_bit_cast(s16x8, qa[u]) : zero8;
-                const s16x8 bf = nok ? __builtin_bit_cast(s16x8, qb[u]) : (one ? ones8 : zero8);
-                acc = Mfma<T>::run(af, bf, acc);
-            }
-            pk = pend;
-        } else
-#endif
         if (aligned) {
             // 4 k-steps (64 pixels) per iteration: all eight 16-byte loads are issued before the first MFMA needs them
             for (; pk + 64 <= pend; pk += 64) {
@@ -826,11 +765,7 @@ wgrad_body(const T *__restrict__ dy, const T *__restrict__ x, float *__restrict_
         for (int r = 0; r < 16; ++r) {
             const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
             const int cn = n0 + col;
-#ifdef OSS_EXP_WGRAD_NOSTORE   // timing experiment: results not written
-            if (row < M && cn < NB && acc[r] == 123456.789f) {
-#else
             if (row < M && cn < NB) {
-#endif
                 const size_t drow = ((size_t)(row / Mh) * G + g) * Mh + row % Mh;  // destination row of (group g, row)
                 if (cn < N) pb[drow * N + cn] = acc[r];
                 else pb[(size_t)G * M * N + row] = acc[r];   // dbias (only ever with G == 1)

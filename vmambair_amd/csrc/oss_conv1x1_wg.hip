@@ -82,16 +82,8 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
     // PT = 128, 192 at PT = 64) put them at 0,64,128,192 | 32,96,160,224: one sweep, no overlap.
     // (b) The output staging tile (PT = 128): PT + 16, with 4-byte writes and a rotated read-back (below).
     constexpr int K = 16 * KS, NCT = PT / 32;
-#ifdef OSS_EXP_WG_OLD_PITCH   // (OSS_EXP_*: A-B timing builds only, tools/build_experiment.sh)
-    constexpr int PX = PT + 8;
-#else
     constexpr int PX = PT + 32;
-#endif
-#ifdef OSS_EXP_WG_OLD_EPI
-    constexpr bool kPairEpi = false;
-#else
     constexpr bool kPairEpi = !RES && PT == 128;
-#endif
     constexpr int PITCH = kPairEpi ? PT + 16 : PT + 8;   // output staging tile
     using OT = typename std::conditional<RES, float, T>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char wg_smem[];
@@ -108,18 +100,6 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int k0 = ks * 16 + kg * 8;
-#ifdef OSS_EXP_WG_HALF_W   // TIMING ONLY (wrong results): half of the weight bytes -- what 16-bit master copies would cost to load
-            if constexpr (!WT) {
-                r.lo[ks] = *reinterpret_cast<const f32x4 *>(w + (size_t)mrow * K + k0);
-                r.hi[ks] = r.lo[ks];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    r.lo[ks][e] = w[(size_t)(k0 + e) * M + mrow];
-                    r.hi[ks][e] = r.lo[ks][e];
-                }
-            }
-#else
             if constexpr (!WT) {
                 r.lo[ks] = *reinterpret_cast<const f32x4 *>(w + (size_t)mrow * K + k0);
                 r.hi[ks] = *reinterpret_cast<const f32x4 *>(w + (size_t)mrow * K + k0 + 4);
@@ -130,7 +110,6 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
                     r.hi[ks][e] = w[(size_t)(k0 + 4 + e) * M + mrow];
                 }
             }
-#endif
         }
         r.bl = bias ? bias[mrow] : 0.f;
     };
@@ -323,11 +302,7 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
     }
 }
 
-#ifdef OSS_EXP_WG_OLD_PITCH
-constexpr int kWgXPad = 8;
-#else
 constexpr int kWgXPad = 32;
-#endif
 // (the staging tile is sized for its widest pitch, PT + 16)
 static size_t wg_lds_bytes(int K, int pt, bool res) { return (size_t)K * 2 * (pt + kWgXPad) + (size_t)4 * 32 * (res ? 4 : 2) * (pt + 16) + 2 * (size_t)K * sizeof(float); }   // + the LayerNorm weight / bias image
 // pixels per workgroup (64 | 128) and the row-tile split (gridDim.z): 0 = by shape, else forced (A-B timing).  Measured

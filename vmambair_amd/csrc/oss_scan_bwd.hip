@@ -215,13 +215,8 @@ oss_scan_bwd_kernel(const oss_scan_bwd_params p, const BwdWs ws) {
                 float dA_acc = 0.f;
 #pragma unroll
                 for (int k = I / 4 - 1; k >= 0; --k) {
-#ifdef OSS_EXP_NO_REREAD  // (timing experiments only: tools/build_experiment.sh) sensitivity to the B/C tile reads
-                    const f32x4 b4 = f32x4{dl[4 * k], dl[4 * k + 1], dl[4 * k + 2], dl[4 * k + 3]};
-                    const f32x4 c4 = f32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]};
-#else
                     const f32x4 b4 = *reinterpret_cast<const f32x4 *>(tb + k * (LPR * 4));
                     const f32x4 c4 = *reinterpret_cast<const f32x4 *>(tc + k * (LPR * 4));
-#endif
 #pragma unroll
                     for (int j = 3; j >= 0; --j) {
                         const int i = 4 * k + j;
@@ -247,7 +242,6 @@ oss_scan_bwd_kernel(const oss_scan_bwd_params p, const BwdWs ws) {
                 if constexpr (SPS == 2) {
                     if (two) state_pass(nn + 1, vB[1], vC[1]);
                 }
-#ifndef OSS_EXP_NO_REDUCE  // (timing experiments only: tools/build_experiment.sh)
                 // ---- cross-row reduction of dB/dC for these states through the slabs
                 __syncthreads();  // the previous states' slice sums have been read
 #pragma unroll
@@ -283,9 +277,6 @@ oss_scan_bwd_kernel(const oss_scan_bwd_params p, const BwdWs ws) {
                         }
                     }
                 }
-#else
-                if (vB[0][0] + vC[0][I - 1] == 12345.678f) ws_bc[0] = vB[0][1];  // keep the values alive
-#endif
             }
         }
         // ---- per-element outputs (bwd_kernel.cuh:151,200-203,228-245)
@@ -651,27 +642,19 @@ static int launch_bwd(const oss_scan_bwd_params &p, hipStream_t stream, LaunchTi
     return launch_finish<T>(p, ws, wdD, wdb, stream);
 }
 
-#ifndef OSS_CARRY_WAVES
-#define OSS_CARRY_WAVES 0   // 0 = the main kernel's row tile
-#endif
-constexpr int kCarryWaves = OSS_CARRY_WAVES;
-
 // round-2 kernel (oss_scan_bwd_v2.h): lane-resident per-state scalars, register-prefetched tiles, one barrier per state
 template <typename T, int WAVES, int NBB, int MINW, bool FD = false, bool PB = false>
 static int launch_bwd2(const oss_scan_bwd_params &p, int seg_req, hipStream_t stream, LaunchTimer *timer) {
     if constexpr (!FD) {
-        if (p.f.dt_weight) {
-            if constexpr (kBuildFusedDt) return launch_bwd2<T, WAVES, NBB, MINW, true>(p, seg_req, stream, timer);
-            else return OSS_ERR_SHAPE;   // this library was built without OSS_WITH_FUSED_DT
-        }
+        if (p.f.dt_weight) return launch_bwd2<T, WAVES, NBB, MINW, true>(p, seg_req, stream, timer);
     }
     constexpr int TC = 512;
     const oss_scan_fwd_params &f = p.f;
     const int rows_per_group = f.dim / f.n_groups;
     const int tiles = (rows_per_group + WAVES - 1) / WAVES;
     if constexpr (!PB && kPartialsBf16Ok<T, FD>) {
-        // bf16 row-tile partials (oss_scan_bwd_v2.h: kV2Bf16Partials): only when THIS call asks for them (tune_partials == 2)
-        const bool lane_states = kBuildLaneStates && f.hs != nullptr;
+        // bf16 row-tile partials (oss_scan_bwd_v2.h: kPartialsBf16Ok): only when THIS call asks for them (tune_partials == 2)
+        const bool lane_states = f.hs != nullptr;
         if (p.tune_partials == 2 && !lane_states)
             return launch_bwd2<T, WAVES, NBB, MINW, false, true>(p, seg_req, stream, timer);
     }
@@ -697,19 +680,19 @@ static int launch_bwd2(const oss_scan_bwd_params &p, int seg_req, hipStream_t st
     if (rc != OSS_OK) return rc;
     g_last_bwd_segments.store(n_seg);
     // lane states saved by the forward pass (f.hs): the kernels that load them instead of re-running the forward recurrence
-    const bool hs = kBuildLaneStates && !FD && !PB && f.hs != nullptr;
+    const bool hs = !FD && !PB && f.hs != nullptr;
     // two tile buffers, two slab buffers (+ dt weights | + two buffers of this wave's lane states)
-    const bool slab_q = kV2SlabQ && !FD && !(hs && WAVES > 8);   // oss_scan_bwd2_kernel: SQ
+    const bool slab_q = !FD && !(hs && WAVES > 8);   // oss_scan_bwd2_kernel: SQ
     const size_t smem = sizeof(float) * (4 * (size_t)NBB * TC + 4 * (size_t)WAVES * (slab_q ? kSlabA : TC) +
                                          (FD ? WAVES * kMaxDtRank : 0) + (hs ? 2 * (size_t)WAVES * NBB * 64 : 0));
     g_last_bwd_lane_states.store(hs ? 1 : 0);
     if constexpr (!FD) {
         if (n_seg > 1) {
             const BwdSeg sg{carry, n_seg, cps, csub, ccps, n_cseg};
-            // the carry pass is per ROW (nothing is summed over rows), so its row tile is free: 4-row workgroups (three times the
-            // workgroups, several per CU) measured SLOWER than the main kernel's tile -- u:(4,192,16384) 0.355 against 0.340 ms for
+            // the carry pass is per ROW (nothing is summed over rows), so its row tile is free; it uses the main kernel's: 4-row
+            // workgroups (three times the workgroups, several per CU) measured SLOWER -- u:(4,192,16384) 0.355 against 0.340 ms for
             // the whole call -- because every workgroup stages the group's C rows again
-            constexpr int CW = kCarryWaves > 0 ? kCarryWaves : WAVES;
+            constexpr int CW = WAVES;
             const int ctiles = (rows_per_group + CW - 1) / CW;
             auto kc = oss_scan_bwd_carry_kernel<T, CW>;
             if (timer) { timer->segmented(); timer->begin(stream); }
@@ -718,7 +701,7 @@ static int launch_bwd2(const oss_scan_bwd_params &p, int seg_req, hipStream_t st
                                stream, p, sg, ctiles);
             static LdsGate gate_s, gate_sh;
             bool launched = false;
-            if constexpr (kBuildLaneStates && !PB) {
+            if constexpr (!PB) {
                 if (hs) {
                     auto km = oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, true, true>;
                     if (const int e = gate_sh.ensure(reinterpret_cast<const void *>(km), smem)) return e;
@@ -736,7 +719,7 @@ static int launch_bwd2(const oss_scan_bwd_params &p, int seg_req, hipStream_t st
             if (rc != OSS_OK) return rc;
             return launch_finish<T, PB>(p, ws, wdD, wdb, stream, n_seg);
         }
-        if constexpr (kBuildLaneStates && !PB) {
+        if constexpr (!PB) {
             if (hs) {
                 static LdsGate gate_h;
                 rc = launch_main(oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, false, true>, smem, gate_h, wgs, WAVES * 64, p, ws,

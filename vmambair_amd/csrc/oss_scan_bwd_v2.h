@@ -90,34 +90,8 @@ __device__ __forceinline__ f32x4 quad_to_f32(const RawQuad<T> &r, bool rev) {
 // FD: delta computed inside the scan from the rank-R factor z (include/vmambair_oss.h: dt_weight); the kernel then emits the
 // gradient of z (summed over the rows of the group: slab rounds like dB / dC, two rank rows per round) and the per-row
 // gradient of dt_weight instead of ddelta.
-#ifdef OSS_EXP_V2_GROUP_PRO
-constexpr bool kV2GroupPro = true;
-#else
-constexpr bool kV2GroupPro = false;
-#endif
-#ifdef OSS_EXP_V2_GROUP_EPI
-constexpr bool kV2GroupEpi = true;
-#else
-constexpr bool kV2GroupEpi = false;
-#endif
-#ifdef OSS_EXP_V2_HCV_EARLY
-constexpr bool kV2HcvEarly = true;
-#else
-constexpr bool kV2HcvEarly = false;
-#endif
 // round 4: (a) the slab in a bank-conflict-free image (SlabQ below) and (b) the chunk-edge factor exp2(A delta_first) of all
-// states as ONE v_exp_f32 per chunk (lane n = state n) instead of one per state pass.  OSS_EXP_V2_OLD_SLAB / _OLD_AEDGE
-// restore the round-2 forms for A-B timing (tools/build_experiment.sh).
-#ifdef OSS_EXP_V2_OLD_SLAB
-constexpr bool kV2SlabQ = false;
-#else
-constexpr bool kV2SlabQ = true;
-#endif
-#ifdef OSS_EXP_V2_OLD_AEDGE
-constexpr bool kV2EdgeLanes = false;
-#else
-constexpr bool kV2EdgeLanes = true;
-#endif
+// states as ONE v_exp_f32 per chunk (lane n = state n) instead of one per state pass.
 // round 6: the workgroup's dB / dC row-tile partials -- written here, re-read by oss_scan_bwd_finish -- are
 // 268 of the call's 417 MB of HBM traffic at u:(8,384,4096) bf16 (algorithmic: 142).  OPT-IN per call (oss_scan_bwd_params.
 // tune_partials = 2, bf16 I/O only): the partials (each already the fp32 sum of the tile's <= 12 rows) go out as bf16 -- half the
@@ -126,13 +100,8 @@ constexpr bool kV2EdgeLanes = true;
 // mantissa BEFORE the tiles are summed, an absolute error of 2^-9 x |partial| that survives when the tiles cancel -- at the
 // reference's own test grid (randn inputs, |dB| up to 83) one element in 131 072 left the reference's bf16 tolerance (atol 5e-2,
 // test_selective_scan.py:400,490-502) with only TWO tiles.  The default keeps the reference's fp32 accumulation
-// (cus/selective_scan_bwd_kernel.cuh:208-221) to the letter.  OSS_EXP_V2_F32_PARTIALS compiles the bf16 form out.
-#ifdef OSS_EXP_V2_F32_PARTIALS
-constexpr bool kV2Bf16Partials = false;
-#else
-constexpr bool kV2Bf16Partials = true;
-#endif
-template <typename T, bool FD> constexpr bool kPartialsBf16Ok = kV2Bf16Partials && !FD && std::is_same<T, bf16_t>::value;
+// (cus/selective_scan_bwd_kernel.cuh:208-221) to the letter.
+template <typename T, bool FD> constexpr bool kPartialsBf16Ok = !FD && std::is_same<T, bf16_t>::value;
 // SlabQ: one row's dB (or dC) terms of one state, 512 scan positions = 64 lanes x 2 quads.  The round-2 image was time order
 // (lane p wrote its quads at floats 8p and 8p + 4: a 32-byte lane stride, so a 16-lane phase of a ds_write_b128 covered only
 // half of the 64 banks, two-way conflicts on every slab write -- SQ_LDS_BANK_CONFLICT 31 % of the LDS cycles,
@@ -188,7 +157,7 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
     // workgroup: 32 KB of tiles + 110.6 KB of SlabQ slabs + 24.6 KB of lane states is 167 KB, over the 160 KB of a workgroup -- since
     // round 4's SlabQ image every `hs` call of variant 10 returned OSS_ERR_SHAPE (an opt-in build feature whose tests skip on the
     // shipped library: nobody saw it).  The time-order slab (98.3 KB) fits.
-    constexpr bool SQ = kV2SlabQ && !FD && !(HS && WAVES > 8);
+    constexpr bool SQ = !FD && !(HS && WAVES > 8);
     constexpr int SA = SQ ? kSlabA : TC;       // floats per (row, dB | dC) array of the slab
     float *slab = smem + 2 * 2 * NBB * TC;     // [2][ROWS][2][SA]  per-row dB / dC terms of one state; two buffers
     float *sW = slab + 2 * ROWS * 2 * SA;      // FD: [ROWS][kMaxDtRank] dt weights of the workgroup's rows (zero-padded)
@@ -303,7 +272,7 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
         A2v = (f.a_log_form ? -__expf(av) : av) * kLog2e;
     }
     float dln_c = 0.f;  // delta of the first step of the later chunk (wave-uniform); 0 past the end
-    float aev = 1.f;    // lane n: exp2(A_n * dln_c), a_{t+1} across the chunk edge (kV2EdgeLanes)
+    float aev = 1.f;    // lane n: exp2(A_n * dln_c), a_{t+1} across the chunk edge
 
     float dD_acc = 0.f, db_acc = 0.f;
     float dWv = 0.f;   // FD: lane r = gradient of dt_weight[d, r]
@@ -369,30 +338,12 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                 dt_rows_apply<I>(zr, R, rev, dl);
                 unpack_raw_dir<I>(ru, rev, uu);
                 unpack_raw_dir<I>(rg, rev, gg);
-            } else if constexpr (!kV2GroupPro) {
+            } else {
+                // three calls, each with its own wait: as ONE group of loads (with the saved state) it measured 4-12 % slower --
+                // the serial loads hide behind the other waves' arithmetic (profiles/r02_scan_bwd_v2_experiments_raw.txt)
                 load_items_dir<I>(u_row, tl, valid, L, rev, uu);
                 load_items_dir<I>(dt_row, tl, valid, L, rev, dl);
                 load_items_dir<I>(g_row, tl, valid, L, rev, gg);
-            } else {
-                // u, delta, dout of the chunk and the saved forward state as ONE group of loads behind one fast / slow decision:
-                // three load_items_dir calls each end in their own s_waitcnt vmcnt(0) (a branch per call), i.e. three
-                // serial round trips per chunk and wave before any arithmetic (and a fourth for the state)
-                RawItems<T, I> ru, rd, rg;
-                if (raw_fast_ok<I>(u_row, tl, valid, L, rev) && raw_fast_ok<I>(dt_row, tl, valid, L, rev) &&
-                    raw_fast_ok<I>(g_row, tl, valid, L, rev)) {
-                    ru = load_raw_fast<I>(u_row, tl, L, rev);
-                    rd = load_raw_fast<I>(dt_row, tl, L, rev);
-                    rg = load_raw_fast<I>(g_row, tl, L, rev);
-                } else {
-                    ru = load_raw_slow<I>(u_row, tl, valid, L, rev);
-                    rd = load_raw_slow<I>(dt_row, tl, valid, L, rev);
-                    rg = load_raw_slow<I>(g_row, tl, valid, L, rev);
-                }
-                if constexpr (kV2HcvEarly)
-                    hcv = (t0 >= kScanChunk && lane < N) ? x_row[(size_t)(t0 / kScanChunk - 1) * 2 * N + 2 * lane + 1] : 0.f;
-                unpack_raw_dir<I>(ru, rev, uu);
-                unpack_raw_dir<I>(rd, rev, dl);
-                unpack_raw_dir<I>(rg, rev, gg);
             }
             if (!row_valid) {  // a row slot past the end of the group must not contribute to dB/dC
 #pragma unroll
@@ -428,13 +379,13 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
         float S = 0.f;
 #pragma unroll
         for (int i = 0; i < I; ++i) S += dl[i];
-        if constexpr (!HS && (FD || !(kV2GroupPro && kV2HcvEarly))) {   // saved forward state entering this chunk (bwd_kernel.cuh:184); otherwise fetched with the chunk's rows
+        if constexpr (!HS) {   // saved forward state entering this chunk (bwd_kernel.cuh:184)
             const int xi = t0 / kScanChunk - 1;
             hcv = (xi >= 0 && lane < N) ? x_row[(size_t)xi * 2 * N + 2 * lane + 1] : 0.f;
         }
         const float dln_lane = shift_from_next_lane(dl[0], dln_c, seg_last);
         const float Sshift = S - dl[0] + dln_lane;  // sum of delta over steps tl+1 .. tl+I
-        if constexpr (kV2EdgeLanes) aev = exp2_hw(dln_c * A2v);
+        aev = exp2_hw(dln_c * A2v);
         // lane-dependent parts of the slab-sum addresses: a half wave = 32 groups of 4 scan positions x one half of the rows
         const int sl = SPLIT ? (lane & 31) : lane;
         const float *sum_src = slab + (SQ ? (sl & 1) * kSlabK + 4 * (sl >> 1) : 4 * sl) + (SPLIT ? (lane >> 5) * (HR * 2 * SA) : 0);
@@ -477,7 +428,10 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                 }
             }
             // ---- reverse recurrence: element (a_{t+1}, C_t g_t)   (bwd_kernel.cuh:170-193)
-            const float a_edge = kV2EdgeLanes ? lane_get(aev, n) : exp2_hw(dln_c * A2);
+            const float a_edge = lane_get(aev, n);
+            // dln_c stays among this lambda's captures: without it the closure loses a field and the register allocation of every
+            // instantiation shifts (same instructions otherwise) -- drop the line only together with a timing A-B
+            (void)dln_c;
             const float a_nl = shift_from_next_lane(a[0], a_edge, seg_last);
             float dloc = 0.f;
 #pragma unroll
@@ -513,12 +467,8 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                     vB[j] = dh * w[i];
                     vC[j] = gg[i] * hh[i];
                 }
-#ifndef OSS_EXP_V2_NOSLAB   // (OSS_EXP_*: timing experiments only, tools/build_experiment.sh -- results are wrong)
                 *reinterpret_cast<f32x4 *>(sb + (SQ ? kSlabK : 4) * k) = f32x4{vB[0], vB[1], vB[2], vB[3]};
                 *reinterpret_cast<f32x4 *>(sb + SA + (SQ ? kSlabK : 4) * k) = f32x4{vC[0], vC[1], vC[2], vC[3]};
-#else
-                if (vB[0] + vC[3] == 12345.678f) sb[0] = vB[1] + vC[2];
-#endif
             }
             const float dA_sum = segment_sum_to_last<LPR>(dA_acc) + lane_get(dAv, n);
             dAv = lane_set(dAv, lane, n, lane_get(dA_sum, 63));
@@ -529,7 +479,6 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
         // are combined with v_permlane32_swap -- the latency of this sum sits on the critical path of every state (all
         // waves wait for the summing ones at the next barrier), so it is spread as thin as the lanes allow.
         auto slab_sum = [&](int prow0, int prow1, int buf) {   // partial rows of the slab's first / second array
-#ifndef OSS_EXP_V2_NOSUM
             int rw = wave - rot;
             rw += (rw < 0) ? WAVES : 0;
             if (rw < RW) {
@@ -572,7 +521,6 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                     }
                 }
             }
-#endif
             rot += RW;
             rot -= (rot >= WAVES) ? WAVES : 0;
         };
@@ -605,9 +553,7 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                 __builtin_amdgcn_sched_barrier(0);
                 state_pass(n0 + nn, b0, c0, h0s);
                 if (!has1 && have_next) stage_commit(tbuf ^ 1, nn0);   // before the batch's last barrier, which then fences it
-#ifndef OSS_EXP_V2_NOBAR
                 __syncthreads();                       // state n's slabs are complete; buffer par^1 is free again
-#endif
                 slab_sum(n0 + nn, N + n0 + nn, par);
                 par ^= 1;
                 if (has1) {
@@ -619,9 +565,7 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                     __builtin_amdgcn_sched_barrier(0);
                     state_pass(n0 + nn + 1, b1, c1, h1s);
                     if (last && have_next) stage_commit(tbuf ^ 1, nn0);
-#ifndef OSS_EXP_V2_NOBAR
                     __syncthreads();
-#endif
                     slab_sum(n0 + nn + 1, N + n0 + nn + 1, par);
                     par ^= 1;
                 }
@@ -653,21 +597,8 @@ oss_scan_bwd2_kernel(const oss_scan_bwd_params p, const BwdWs ws, const BwdSeg s
                 }
             } else {
                 float raw[I];
-                if constexpr (!kV2GroupEpi) {
-                    load_items_dir<I>(u_row, tl, valid, L, rev, uu);
-                    load_items_dir<I>(dt_row, tl, valid, L, rev, raw);
-                } else {   // u and delta again (not kept across the state loop: registers), as one group of loads
-                    RawItems<T, I> ru, rd;
-                    if (raw_fast_ok<I>(u_row, tl, valid, L, rev) && raw_fast_ok<I>(dt_row, tl, valid, L, rev)) {
-                        ru = load_raw_fast<I>(u_row, tl, L, rev);
-                        rd = load_raw_fast<I>(dt_row, tl, L, rev);
-                    } else {
-                        ru = load_raw_slow<I>(u_row, tl, valid, L, rev);
-                        rd = load_raw_slow<I>(dt_row, tl, valid, L, rev);
-                    }
-                    unpack_raw_dir<I>(ru, rev, uu);
-                    unpack_raw_dir<I>(rd, rev, raw);
-                }
+                load_items_dir<I>(u_row, tl, valid, L, rev, uu);   // u and delta again (not kept across the state loop: registers)
+                load_items_dir<I>(dt_row, tl, valid, L, rev, raw);
 #pragma unroll
                 for (int i = 0; i < I; ++i) {
                     float s = 1.f;

@@ -53,13 +53,9 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
     static_assert(I % 4 == 0, "");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
-#ifdef OSS_EXP_FWD_NO_TILE_PAD   // (OSS_EXP_*: A-B timing builds only, tools/build_experiment.sh)
-    constexpr bool kPad = false;
-#else
-    constexpr bool kPad = true;       // bank-conflict-free staging writes (oss_device.h: tile_off_pad)
-#endif
-    constexpr int TR = kPad ? kTileRowPad<LPR, I> : TC;   // floats per state row of a tile
-    constexpr int PL = kPad ? LPR * 4 + kTilePlanePad<I> : LPR * 4;   // floats between the quads of a lane
+    // padded tiles: bank-conflict-free staging writes (oss_device.h: tile_off_pad)
+    constexpr int TR = kTileRowPad<LPR, I>;              // floats per state row of a tile
+    constexpr int PL = LPR * 4 + kTilePlanePad<I>;       // floats between the quads of a lane
     float *sB = smem;                 // [kNB][TR]
     float *sC = smem + kNB * TR;      // [kNB][TR]
     float *carH = smem + 2 * kNB * TR;               // [dstate][ROWS]   h entering the chunk
@@ -81,17 +77,12 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
     // u:(8,384,4096): tile = id % 8 dealt a group's eight tiles to the eight XCDs).  Speed only: nothing depends on placement.
     int bid = blockIdx.x, tile;
     const int ns = SEG == 0 ? 1 : (SEG == 1 ? (sg.n_seg - 1) * sg.csub : sg.n_seg);   // the last segment has no successor: no local pass
-#ifdef OSS_EXP_FWD_NO_XCD   // (OSS_EXP_*: A-B timing builds only, tools/build_experiment.sh)
-    constexpr bool kXcdOrder = false;
-#else
-    constexpr bool kXcdOrder = true;
-#endif
     // (round 5) Generalised from "the number of sets divides by 8" to "the number of WORKGROUPS divides by 8": XCD x (ids with residue x)
     // takes the x-th eighth of the (set, tile) pairs in set-major order, so it works on whole sets except at the two ends of its
     // run.  u:(1,384,25600) in 9 segments is 36 sets x 8 tiles: the old rule did not apply and every XCD fetched every set's B / C
     // (FETCH 87 MB for 36 MB of inputs, profiles/r05_pmc_FETCH_SIZE_realsr.txt).
     const int total = p.batch * p.n_groups * ns * tiles_per_group;
-    if (kXcdOrder && total % 8 == 0) {
+    if (total % 8 == 0) {
         const int i = (bid & 7) * (total >> 3) + (bid >> 3);
         tile = i % tiles_per_group;
         bid = i / tiles_per_group;
@@ -121,7 +112,7 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
     const int n_xchunks = (L + kScanChunk - 1) / kScanChunk;
     float *x_row = p.x + ((size_t)b * p.dim + d) * n_xchunks * 2 * N;
     const size_t hs_stride = lane_state_stride(L);
-    float *hs_line = (kBuildLaneStates && SEG != 1 && p.hs) ? p.hs + ((size_t)b * p.dim + d) * N * hs_stride : nullptr;
+    float *hs_line = (SEG != 1 && p.hs) ? p.hs + ((size_t)b * p.dim + d) * N * hs_stride : nullptr;
 
     // carries start at (h, P) = (0, 1); A is pre-scaled once (fwd_kernel.cuh:125-127)
     for (int idx = tid; idx < N * ROWS; idx += NT) {
@@ -200,7 +191,7 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
         for (int n0 = 0; n0 < N; n0 += kNB) {
             const int nb = min(kNB, N - n0);
             __syncthreads();  // everyone is done with the previous tile (and the carry init)
-            stage_bc_tiles<T, LPR, I, NT, SEG != 1, kPad>(sB, sC, gB + (int64_t)n0 * p.B_dstate_stride,
+            stage_bc_tiles<T, LPR, I, NT, SEG != 1, true>(sB, sC, gB + (int64_t)n0 * p.B_dstate_stride,
                                           gC + (int64_t)n0 * p.C_dstate_stride, p.B_dstate_stride,
                                           p.C_dstate_stride, nb, t0, L, rev, tid);
             __syncthreads();
@@ -286,20 +277,13 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
 template <typename T, int LPR, int I, int WAVES, bool FD = false>
 static int launch_fwd(const oss_scan_fwd_params &p, int seg_req, hipStream_t stream) {
     if constexpr (!FD) {
-        if (p.dt_weight) {
-            if constexpr (kBuildFusedDt) return launch_fwd<T, LPR, I, WAVES, true>(p, seg_req, stream);
-            else return OSS_ERR_SHAPE;   // this library was built without OSS_WITH_FUSED_DT
-        }
+        if (p.dt_weight) return launch_fwd<T, LPR, I, WAVES, true>(p, seg_req, stream);
     }
     constexpr int ROWS = WAVES * (64 / LPR);
     constexpr int TC = LPR * I;
     const int rows_per_group = p.dim / p.n_groups;
     const int tiles = (rows_per_group + ROWS - 1) / ROWS;
-#ifdef OSS_EXP_FWD_NO_TILE_PAD
-    constexpr int TR = TC;
-#else
     constexpr int TR = kTileRowPad<LPR, I>;
-#endif
     const size_t smem = sizeof(float) * (2 * (size_t)kNB * TR + 3 * (size_t)p.dstate * ROWS);
     if constexpr (!(LPR == 64 && I == 4 && WAVES == 4)) {
         // large dstate: tiles + per-row carries no longer fit 160 KiB -> the small-shape variant (4 rows, 256-step chunks)

@@ -172,7 +172,7 @@ std::vector<Tensor> scan_fwd(const Tensor &u, const Tensor &delta, const Tensor 
     Tensor x = at::empty({d.batch, d.dim, (int64_t)n_chunks, 2 * d.dstate}, u.options().dtype(at::kFloat));
     OptTensor hs;
     TORCH_CHECK(!want_hs || (oss_scan_features() & OSS_FEATURE_LANE_STATES),
-                "want_hs: libvmambair_oss.so was built without the lane-state scan form (-DOSS_WITHOUT_LANE_STATES)");
+                "want_hs: this libvmambair_oss.so does not report the lane-state scan form (oss_scan_features)");
     if (want_hs)
         hs = at::empty({(int64_t)oss_scan_lane_state_floats((int)d.batch, (int)d.dim, (int)d.seqlen, (int)d.dstate)},
                        u.options().dtype(at::kFloat));
