@@ -707,6 +707,40 @@ int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, d
                       int64_t b_batch_stride, int64_t b_channel_stride, int64_t b_row_stride, int crop_border, int flags,
                       oss_stream_t stream);
 
+/* Training batches cut on the device (oss_pairs.hip): a pool of decoded image pairs resident in device memory, a counter-based draw
+ * and one gather launch per batch -- paired_random_crop, augment / random_augmentation (Deraining/basicsr/data/transforms.py:24-83,
+ * :136-200, :223-275), img2tensor(bgr2rgb, float32) of img / 255. (utils/img_util.py:9-40) and EnlargedSampler's rank-strided epoch
+ * permutation, with no host work, no copy from the host, no atomics and no allocation: both calls can be captured into a hipGraph.
+ *   pool      flat uint8 buffer of HWC images, `channels` (1 or 3) interleaved bytes per pixel, any byte alignment
+ *   table     (n_pairs, 4) int64 in device memory: gt_offset, lq_offset (bytes into pool), lq_h, lq_w; the GT image is
+ *             (scale lq_h, scale lq_w); with scale == 1 LQ and GT are still two images
+ *   samples   (batch, 4) int in device memory: pair_index, top, left (LQ pixels), code; code bit 0 = horizontal flip, bit 1 =
+ *             vertical flip, bit 2 = transpose, applied in that order (the 8 elements of the dihedral group: every mode of
+ *             data_augmentation is exactly one code)
+ * oss_pairs_draw (one single-workgroup launch) fills `samples`: it reads the sample counter c (*counter), gives sample b the
+ * per-rank position q = c + b and the global position g = q * world + rank, epoch = g div n_pairs, pair = perm_epoch(g mod n_pairs)
+ * -- a keyed bijection of [0, n_pairs): 4 Feistel rounds over the next even number of bits with cycle walking, round function
+ * word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter (half, round | epoch_hi << 8, epoch_lo, 0x7065726d) -- so all ranks
+ * together see every pair once per epoch; top, left, code = words 0, 1, 2 of the Philox block with counter (g lo, g hi, 0x63726f70,
+ * 0): top = (word * (lq_h - patch + 1)) >> 32, left likewise, code = (word >> 29) masked by flags (OSS_PAIRS_HFLIP admits bit 0,
+ * OSS_PAIRS_ROT bits 1 and 2).  It stores c + batch after every thread has read c, so a replayed launch continues the sequence.
+ * oss_pairs_gather writes lq (batch, channels, patch_h, patch_w) and gt (batch, channels, scale patch_h, scale patch_w), float,
+ * contiguous, from ONE launch: value = float(byte) / 255.0f correctly rounded, channel order reversed when swap_rb != 0 and
+ * channels == 3.  Rectangular patches (whole validation images) are taken with codes 0-3; bit 2 needs patch_h == patch_w.  The
+ * kernel never reads outside an image: a rectangle, pair index or offset that does not fit is clamped, what cannot be read is
+ * written as 0 and *clamped (an int in device memory the caller zeroed) is set to 1.
+ * oss_pairs_ok is a pure host query: channels 1 or 3, 1 <= scale <= 64, 1 <= patch sides, scale * side <= 2^20, 1 <= batch <= 65535
+ * and at most 65535 tiles of 32 x 32 pixels per sample (LQ + GT).  oss_pairs_philox evaluates one Philox4x32-10 block (4 counter
+ * words, 2 key words -> 4 words) on the HOST from the text the kernels are compiled from. */
+#define OSS_PAIRS_HFLIP 1
+#define OSS_PAIRS_ROT 2
+int oss_pairs_philox(const uint32_t *counter, const uint32_t *key, uint32_t *out);
+int oss_pairs_ok(int channels, int scale, int patch_h, int patch_w, int batch);
+int oss_pairs_draw(const int64_t *table, int n_pairs, int64_t *counter, int *samples, int batch, int patch, int64_t seed, int rank,
+                   int world, int flags, oss_stream_t stream);
+int oss_pairs_gather(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq, float *gt,
+                     int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb, oss_stream_t stream);
+
 /* Algorithmic bytes of the block's NON-scan launches, by kernel family (round 6; bench.py `roofline.non_scan`).  While counting
  * is on, every entry point of this header that launches a kernel adds the bytes its launch must move at minimum (each operand
  * read once, each result written once, fp32 master weights included, scratch partials not) to its family's counter -- host-side
