@@ -220,11 +220,33 @@ def test_compiled_torch_boundary_is_built_and_registers_its_ops():
     ops = _host.ops()
     s = str(ops.scan_bwd.default._schema)
     assert "Tensor(a!)? dbc_into" in s and str(ops.scan_fwd.default._schema).endswith("-> Tensor[]")
-    _host.use("ctypes")
-    try:
-        assert _host.mode() == "ctypes" and _host.ops() is None
-    finally:
-        _host.use(None)
+
+
+def test_missing_torch_boundary_is_a_hard_error(monkeypatch, tmp_path):
+    """no fallback: without lib/libvmambair_torch.so the scan ops raise and name the build command, like _capi.load()"""
+    from vmambair_amd import _host
+    monkeypatch.setattr(_host, "_ops", None)          # restored afterwards: later tests load normally
+    monkeypatch.setattr(_build, "HOST_LIB", str(tmp_path / "libvmambair_torch.so"))
+    with pytest.raises(RuntimeError, match=r"libvmambair_torch\.so is missing.*__graft_entry__ as g; g\.build\(\)"):
+        _host.ops()
+    with pytest.raises(RuntimeError, match="is missing"):
+        _host.mode()
+    assert _host._ops is None
+
+
+def test_stale_torch_boundary_is_refused_before_it_is_loaded(monkeypatch):
+    """a host library compiled against another revision of include/vmambair_oss.h raises with abi_mismatch()'s reason and is
+    never handed to torch.ops.load_library"""
+    from vmambair_amd import _host
+    loaded = []
+    monkeypatch.setattr(_host, "_ops", None)
+    monkeypatch.setattr(_host, "abi_mismatch", lambda: "compiled against another revision (test)")
+    monkeypatch.setattr(torch.ops, "load_library", loaded.append)
+    with pytest.raises(RuntimeError, match=r"compiled against another revision \(test\)"):
+        _host.ops()
+    assert loaded == [] and _host._ops is None
+    monkeypatch.undo()
+    assert _host.abi_mismatch() is None and hasattr(_host.ops(), "scan_fwd")
 
 
 def test_shape_rules_of_the_fused_kernels_are_pure_host_queries():

@@ -602,3 +602,20 @@ def test_csrc_has_no_compile_time_switches():
     assert conditionals == [("oss_capi.hip", "#ifndef OSS_SCAN_BUILD_ID")]
     for f in csrc + sorted(glob.glob(os.path.join(pkg, "*.py"))):
         assert not re.search(r"OSS_EXP_|OSS_WITHOUT_", open(f).read()), f
+
+
+def test_scan_has_one_host_boundary():
+    """the compiled layer (csrc_host/oss_torch_host.cpp) is the only code that fills the scan's parameter structs and calls the
+    C ABI's scan entry points: ``ops/scan.py`` holds no second copy, and nothing selects between boundaries"""
+    import glob
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    scan = open(os.path.join(root, "vmambair_amd", "ops", "scan.py")).read()
+    assert "ScanFwdParams" not in scan and "oss_scan_fwd(" not in scan
+    assert "ScanBwdParams" not in scan and "oss_scan_bwd(" not in scan
+    for sub in ("vmambair_amd", "tools"):
+        files = [f for f in glob.glob(os.path.join(root, sub, "**"), recursive=True)
+                 if os.path.isfile(f) and f.endswith((".py", ".cpp", ".h", ".hip", ".sh", ".md", ".txt"))]
+        assert files, sub
+        for f in files:
+            assert "VMAMBAIR_HOST" not in open(f, errors="replace").read(), f

@@ -1,5 +1,5 @@
-"""GPU parity tests of the HIP selective scan, THROUGH THE C ABI (vmambair_amd.ops -> ctypes ->
-libvmambair_oss.so), against the CPU oracle on the same seeded inputs and against the golden
+"""GPU parity tests of the HIP selective scan, THROUGH THE C ABI (vmambair_amd.ops ->
+libvmambair_torch.so -> libvmambair_oss.so), against the CPU oracle on the same seeded inputs and against the golden
 vectors of the reference.
 
 The grid is the reference's own (Mamba/kernels/selective_scan/test_selective_scan.py:365-502):
@@ -784,12 +784,10 @@ def test_opt_in_bf16_row_tile_partials_change_only_the_row_tile_sums(rows):
             assert torch.equal(a, f), n
 
 
-@pytest.mark.parametrize("boundary", ["c++", "ctypes"])
-def test_per_call_tuning_fields_select_the_launch_shape_without_global_state(boundary):
+def test_per_call_tuning_fields_select_the_launch_shape_without_global_state():
     """(round 6) ``oss_scan_fwd_params.tune_*`` / ``oss_scan_bwd_params.tune_*``: variant, time segments and the
     carry split of ONE call, with the process-global setters left at their defaults -- bit-identical to the same launch shape
-    forced through the test-only setters, on both host boundaries; and a per-call field wins over a contradicting global."""
-    from vmambair_amd import _host
+    forced through the test-only setters; and a per-call field wins over a contradicting global."""
     lib = _capi.load()
     u, dl, A, B, C, D, b, g = to_dev(make_inputs(2, 48, 16, 4, 4096, torch.float32, seed=21))
 
@@ -801,7 +799,6 @@ def test_per_call_tuning_fields_select_the_launch_shape_without_global_state(bou
         torch.cuda.synchronize()
         return [out] + [t for t in grads if t is not None], shape_f, shape_b
 
-    _host.use(boundary)
     try:
         per_call, sf, sb = call((0, 2, 4), (13, 2, 4))
         assert sf == (0, 2) and sb == (13, 2)
@@ -814,7 +811,6 @@ def test_per_call_tuning_fields_select_the_launch_shape_without_global_state(bou
         assert wf == (4, 1) and wb == (1, 1)
     finally:
         lib.oss_scan_set_segments(-1, -1); lib.oss_scan_set_variant(-1, -1); lib.oss_scan_set_carry_split(0)
-        _host.use(None)
     assert hf != sf or hb != sb, "the heuristic picked the forced shape: the test shows nothing"
     for a, c in zip(per_call, via_globals):
         assert torch.equal(a, c)
@@ -929,15 +925,15 @@ def test_segmented_scan_at_inference_tile_length(itype):
 
 
 # ------------------------------------------------------------------------------------------------
-# the two host boundaries over the same C ABI: compiled TORCH_LIBRARY layer (default) and ctypes
+# the host boundary: the compiled TORCH_LIBRARY layer over the C ABI
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("itype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 def test_compiled_and_ctypes_boundaries_agree(itype):
-    """csrc_host/oss_torch_host.cpp (what cus/selective_scan.cpp:157-349 is to the reference) and the ctypes marshalling in
-    ops/scan.py fill the same parameter struct: bit-identical tensors, same None pattern, same errors; strided B / C views,
-    omni arguments and the in-place dB / dC rows included"""
+    """contract of csrc_host/oss_torch_host.cpp (what cus/selective_scan.cpp:157-349 is to the reference; the test keeps the name it
+    had while ops/scan.py carried a ctypes copy of that layer): strided B / C views of x_dbl, omni arguments and the in-place
+    dB / dC rows give the oracle's values, seven entries with None for what is absent, the reference's errors, empty batches"""
     from vmambair_amd import _host
-    assert _host.mode() == "c++", "the compiled boundary must be the default on a GPU box (build() makes it)"
+    assert _host.mode() == "c++", "the compiled boundary must load on a GPU box (build() makes it)"
     torch.manual_seed(0)
     Bsz, K, rows, L, R, N = 2, 4, 12, 1300, 3, 16
     xdbl = torch.randn(Bsz, K, R + 2 * N, L, device=DEV).to(itype)
@@ -948,36 +944,47 @@ def test_compiled_and_ctypes_boundaries_agree(itype):
     dout = torch.randn(Bsz, 2 * rows, L, device=DEV).to(itype)
     Bm, Cm = xdbl[:, :, R:R + N], xdbl[:, :, R + N:]
     kw = dict(rev_group_start=2, u_row_mod=2 * rows, a_log_form=True)
-    res = {}
-    for mode in ("c++", "ctypes"):
-        _host.use(mode)
-        try:
-            out, x = vmambair_amd.selective_scan_fwd(x2, delta, A_log, Bm, Cm, D, bias, True, 1, **kw)
-            into = torch.zeros_like(xdbl)
-            g = vmambair_amd.selective_scan_bwd(x2, delta, A_log, Bm, Cm, D, bias, dout, x, True, 1, dout_row_mod=2 * rows,
-                                                dbc_into=into, **kw)
-            plain = vmambair_amd.selective_scan_bwd(x2.repeat(1, 2, 1), delta, -torch.exp(A_log), Bm.contiguous(), Cm.contiguous(),
-                                                    None, None, dout.repeat(1, 2, 1), None if L <= 256 else x, False, 1)
-            with pytest.raises(RuntimeError, match="delta, B, C must have u's dtype"):
-                vmambair_amd.selective_scan_fwd(x2, delta.float() if itype != torch.float32 else delta.half(), A_log, Bm, Cm, D, bias, True, 1, **kw)
-            with pytest.raises(RuntimeError, match="dout must have u's shape"):
-                vmambair_amd.selective_scan_bwd(x2, delta, A_log, Bm, Cm, D, bias, dout[:, :5], x, True, 1, dout_row_mod=2 * rows, **kw)
-            e_out, e_x = vmambair_amd.selective_scan_fwd(x2[:0], delta[:0], A_log, Bm[:0], Cm[:0], D, bias, True, 1, **kw)
-            assert e_out.shape == (0, K * rows, L) and e_x.shape[0] == 0
-        finally:
-            _host.use(None)
-        res[mode] = (out, x, g, into, plain)
-    a, b = res["c++"], res["ctypes"]
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[3], b[3])
-    for ga, gb in ((a[2], b[2]), (a[4], b[4])):
-        assert len(ga) == len(gb) == 7
-        for t1, t2 in zip(ga, gb):
-            assert (t1 is None) == (t2 is None)
-            if t1 is not None:
-                assert t1.dtype == t2.dtype and t1.shape == t2.shape and torch.equal(t1, t2)
-    assert a[4][5] is None and a[4][6] is None, "absent D / delta_bias come back as None through both boundaries"
-    # dB / dC of the in-place form are views of dbc_into's last rows in both
-    assert a[2][3].data_ptr() == a[3][:, :, R:R + N].data_ptr() and a[2][4].data_ptr() == a[3][:, :, R + N:].data_ptr()
+    out, x = vmambair_amd.selective_scan_fwd(x2, delta, A_log, Bm, Cm, D, bias, True, 1, **kw)
+    into = torch.zeros_like(xdbl)
+    g = vmambair_amd.selective_scan_bwd(x2, delta, A_log, Bm, Cm, D, bias, dout, x, True, 1, dout_row_mod=2 * rows,
+                                        dbc_into=into, **kw)
+    plain = vmambair_amd.selective_scan_bwd(x2.repeat(1, 2, 1), delta, -torch.exp(A_log), Bm.contiguous(), Cm.contiguous(),
+                                            None, None, dout.repeat(1, 2, 1), None if L <= 256 else x, False, 1)
+    with pytest.raises(RuntimeError, match="delta, B, C must have u's dtype"):
+        vmambair_amd.selective_scan_fwd(x2, delta.float() if itype != torch.float32 else delta.half(), A_log, Bm, Cm, D, bias, True, 1, **kw)
+    with pytest.raises(RuntimeError, match="dout must have u's shape"):
+        vmambair_amd.selective_scan_bwd(x2, delta, A_log, Bm, Cm, D, bias, dout[:, :5], x, True, 1, dout_row_mod=2 * rows, **kw)
+    e_out, e_x = vmambair_amd.selective_scan_fwd(x2[:0], delta[:0], A_log, Bm[:0], Cm[:0], D, bias, True, 1, **kw)
+    assert e_out.shape == (0, K * rows, L) and e_x.shape[0] == 0
+    assert len(g) == len(plain) == 7
+    assert all(t is not None and t.dtype == (torch.float32 if i in (2, 5, 6) else itype) for i, t in enumerate(g))
+    assert [t is None for t in plain] == [False] * 5 + [True] * 2, "absent D / delta_bias come back as None"
+    assert g[0].shape == (Bsz, K * rows, L) and g[1].shape == delta.shape and g[2].shape == A_log.shape
+    # dB / dC of the in-place form are views of dbc_into's last rows; the rows the call does not own stay untouched
+    assert g[3].data_ptr() == into[:, :, R:R + N].data_ptr() and g[4].data_ptr() == into[:, :, R + N:].data_ptr()
+    assert g[3].shape == Bm.shape and g[4].shape == Cm.shape
+    assert float(into[:, :, :R].abs().max()) == 0.0, "the dt rows of dbc_into belong to oss_proj_dgrad"
+
+    # the omni call against the oracle on the un-shared, un-mirrored problem (as in
+    # test_lane_states_with_time_segments_and_the_omni_form): directions 2, 3 scan the mirrored sequence
+    def mirror(t, per):
+        t = t.cpu().clone()
+        t[:, 2 * per:] = t[:, 2 * per:].flip(-1)
+        return t
+    A = -torch.exp(A_log).cpu()
+    u4, g4, dl4, B4, C4 = mirror(x2.repeat(1, 2, 1), rows), mirror(dout.repeat(1, 2, 1), rows), mirror(delta, rows), mirror(Bm, 1), mirror(Cm, 1)
+    ref_out, _ = oss_oracle.scan_fwd(u4, dl4, A, B4, C4, D.cpu(), bias.cpu(), True, chunk=vmambair_amd.scan_chunk())
+    ref = oss_oracle.scan_bwd(u4, dl4, A, B4, C4, D.cpu(), bias.cpu(), g4, None, True)
+    rtol, atol = TOL[itype]
+    assert_close(out, mirror(ref_out, rows), rtol, atol, "out")
+    assert_close(g[0], mirror(ref[0], rows), rtol * 2, atol * 2, "du")
+    assert_close(g[1], mirror(ref[1], rows), rtol * 5, atol * 10, "ddelta")
+    assert_close(g[3], mirror(ref[3], 1), rtol, atol, "dB")
+    assert_close(g[4], mirror(ref[4], 1), rtol, atol, "dC")
+    wa = 2e-5 if itype == torch.float32 else 2e-3   # sums of batch * L terms: the absolute parts as in check_fwd_bwd
+    assert_close(g[2], ref[2] * A, RTOLW, max(ATOLW * 5, wa * float((ref[2] * A).abs().max())), "dA_log = dA * A")
+    for i, n in ((5, "dD"), (6, "ddelta_bias")):
+        assert_close(g[i], ref[i], RTOLW, max(ATOLW, wa * float(ref[i].abs().max())), n)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,14 +1,13 @@
 """Loader of the compiled torch boundary (``lib/libvmambair_torch.so``, source ``csrc_host/oss_torch_host.cpp``): the C++
-``TORCH_LIBRARY`` twin of the reference's pybind layer (cus/selective_scan.cpp:157-349) for the scan ops.
+``TORCH_LIBRARY`` counterpart of the reference's pybind layer (cus/selective_scan.cpp:157-349) for the scan ops.
 
-``mode()``: ``"c++"`` when the library is built and ``VMAMBAIR_HOST`` is not ``ctypes`` -- then ``ops/scan.py`` hands its
-arguments to ``torch.ops.vmambair_host.scan_fwd / scan_bwd`` -- else ``"ctypes"`` (the Python marshalling in ``ops/scan.py``
-over ``_capi``; kept as the test path, same C ABI underneath).  ``use(mode)`` switches at run time (tests, A-B timing)."""
+``ops()`` loads the library on first use and returns ``torch.ops.vmambair_host`` (``scan_fwd`` / ``scan_bwd``), the only host
+path of ``ops/scan.py``.  As in ``_capi.load()``, a missing library or one built against another revision of
+include/vmambair_oss.h is a hard error: no fallback path exists."""
 from __future__ import annotations
 
 import ctypes as C
 import os
-import warnings
 from typing import Optional
 
 import torch
@@ -16,8 +15,6 @@ import torch
 from . import _build
 
 _ops = None
-_forced: Optional[str] = None
-_stale_reason: Optional[str] = None
 
 
 def abi_mismatch() -> Optional[str]:
@@ -41,33 +38,22 @@ def abi_mismatch() -> Optional[str]:
     return None
 
 
-def _load():
-    global _ops, _stale_reason
-    if _ops is None and _stale_reason is None and os.path.exists(_build.HOST_LIB):
-        _stale_reason = abi_mismatch()
-        if _stale_reason is not None:
-            warnings.warn(_stale_reason + " -- scan calls use the ctypes boundary instead", RuntimeWarning)
-            return None
+def ops():
+    """``torch.ops.vmambair_host``; raises ``RuntimeError`` when the library is missing or stale"""
+    global _ops
+    if _ops is None:
+        if not os.path.exists(_build.HOST_LIB):
+            raise RuntimeError(
+                f"{_build.HOST_LIB} is missing: the compiled torch boundary has not been built "
+                "(run `python -c 'import __graft_entry__ as g; g.build()'`). There is no fallback path.")
+        reason = abi_mismatch()
+        if reason is not None:
+            raise RuntimeError(reason)
         torch.ops.load_library(_build.HOST_LIB)
         _ops = torch.ops.vmambair_host
     return _ops
 
 
-def use(mode: Optional[str]) -> None:
-    """``"c++"``, ``"ctypes"`` or ``None`` (= environment / default)"""
-    global _forced
-    assert mode in (None, "c++", "ctypes")
-    if mode == "c++" and _load() is None:
-        raise RuntimeError(_stale_reason or f"{_build.HOST_LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    _forced = mode
-
-
 def mode() -> str:
-    want = _forced or os.environ.get("VMAMBAIR_HOST", "c++")
-    if want == "ctypes":
-        return "ctypes"
-    return "c++" if _load() is not None else "ctypes"
-
-
-def ops():
-    return _load() if mode() == "c++" else None
+    """``"c++"`` once the library has loaded (the build driver asserts it); raises like ``ops()`` otherwise"""
+    return ops() and "c++"

@@ -5,9 +5,8 @@
 // (Mamba/kernels/selective_scan/csrc/selective_scan/cus/selective_scan.cpp:157-239 fwd, :241-349 bwd).  This file is the same
 // layer over OUR C ABI (include/vmambair_oss.h): TORCH_CHECKs in the reference's order and wording, outputs allocated by the
 // callee, oss_scan_fwd_params / oss_scan_bwd_params filled from sizes and ELEMENT strides, launch on the current HIP stream
-// of u's device, no host synchronisation.  vmambair_amd/ops/scan.py calls these operators when this library is built and
-// keeps its ctypes twin of the same logic as the test path (VMAMBAIR_HOST=ctypes); both produce bit-identical results because
-// both only marshal arguments for libvmambair_oss.so.
+// of u's device, no host synchronisation.  It is the only host path of the scan: vmambair_amd/ops/scan.py hands its arguments
+// to these operators and shapes what they return, and vmambair_amd/_host.py refuses to run without this library.
 //
 // Differences from the reference's functions (all documented in include/vmambair_oss.h / DESIGN.md section 1): x holds one
 // state every oss_scan_chunk() steps; bwd needs no zero-filled outputs and returns dB / dC already cast; the omni extensions
@@ -152,6 +151,12 @@ void fill_fwd(oss_scan_fwd_params &P, const Tensor &u, const Tensor &delta, cons
     P.hs = reinterpret_cast<float *>(const_cast<void *>(ptr(hs)));
 }
 
+// where the gradient of the dt factor lands: the first R rows of dbc_into (the fused-delta form and finish_dt_weight)
+void set_ddt(oss_scan_bwd_params &P, const Tensor &dbc_into) {
+    P.ddt = dbc_into.data_ptr();
+    P.ddt_batch_stride = dbc_into.stride(0); P.ddt_group_stride = dbc_into.stride(1); P.ddt_rank_stride = dbc_into.stride(2);
+}
+
 // cus/selective_scan.cpp:157-239
 // want_hs: also return the lane states (include/vmambair_oss.h: hs) as a third tensor, for scan_bwd's `hs` argument
 std::vector<Tensor> scan_fwd(const Tensor &u, const Tensor &delta, const Tensor &A, const Tensor &B, const Tensor &C,
@@ -270,9 +275,8 @@ std::vector<Tensor> scan_bwd(const Tensor &u, const Tensor &delta, const Tensor 
     P.dout_batch_stride = dout.stride(0); P.dout_d_stride = dout.stride(1);
     P.du_batch_stride = du.stride(0); P.du_d_stride = du.stride(1);
     if (fused) {
-        P.ddt = dbc_into->data_ptr();
+        set_ddt(P, *dbc_into);
         P.ddt_weight = ddtw.data_ptr<float>();
-        P.ddt_batch_stride = dbc_into->stride(0); P.ddt_group_stride = dbc_into->stride(1); P.ddt_rank_stride = dbc_into->stride(2);
     } else {
         P.ddelta_batch_stride = ddelta.stride(0); P.ddelta_d_stride = ddelta.stride(1);
         P.ddelta = ddelta.data_ptr();
@@ -294,8 +298,7 @@ std::vector<Tensor> scan_bwd(const Tensor &u, const Tensor &delta, const Tensor 
         TORCH_CHECK(oss_scan_bwd_finish_dt_ok((int)d.seqlen, (int)w.size(1)), "finish_dt_weight: rank <= 8 and seqlen % 4 == 0");
         P.finish_dt_weight = w.data_ptr<float>();
         P.finish_dt_rank = (int)w.size(1);
-        P.ddt = dbc_into->data_ptr();
-        P.ddt_batch_stride = dbc_into->stride(0); P.ddt_group_stride = dbc_into->stride(1); P.ddt_rank_stride = dbc_into->stride(2);
+        set_ddt(P, *dbc_into);
     }
     hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
     abi_check_once();
