@@ -351,8 +351,8 @@ int oss_conv1x1_dgrad(oss_dtype io, const void *dy, const float *weight, void *d
                       int64_t dy_batch_stride, int64_t dy_channel_stride, oss_stream_t stream);
 size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels);
 /* Tuning override of oss_conv1x1_wgrad / oss_proj_wgrad: MFMA tiles per wave, 0 = 1 x 1 (default), 12 / 21 / 22 = rows x columns
- * of 32 x 32 tiles (fewer re-reads of the operands, fewer waves).  Same results up to the summation order; initial value from
- * the environment variable VMAMBAIR_WGRAD_TILE. */
+ * of 32 x 32 tiles (fewer re-reads of the operands, fewer waves).  Same results up to the summation order; the library starts
+ * at 0. */
 /* Workgroup-level form of oss_conv1x1_fwd / oss_conv1x1_dgrad without residual (oss_conv1x1_wg.hip): cin % 16 == 0, cin <= 192,
  * pixels % 128 == 0, 16-byte aligned tensors; anything else returns OSS_ERR_SHAPE (callers then use the wave-level kernels).
  * transposed_weight = 1: weight is (cin, cout) row-major, i.e. the call is the input gradient of a (cin, cout) convolution. */
@@ -378,12 +378,12 @@ int oss_conv1x1_dgrad_ln_bwd(oss_dtype io, const void *dy, const float *weight, 
                              const float *mean, const float *rstd, const void *skip_grad, void *dx, float *dln_weight, float *dln_bias,
                              float *partials, int batch, int cout, int cin, int pixels, int64_t dy_batch_stride,
                              int64_t dy_channel_stride, oss_stream_t stream);
-/* A-B switches of the dispatch inside oss_conv1x1_fwd / _dgrad: on = 0 never takes the workgroup-level kernel (env
- * VMAMBAIR_CONV1X1_WG=0); pixels = 64 | 128 forces its tile width, 0 = by grid size */
+/* A-B switches of the dispatch inside oss_conv1x1_fwd / _dgrad: on = 0 never takes the workgroup-level kernel (the
+ * library starts with on = 1); pixels = 64 | 128 forces its tile width, 0 = by grid size (the start value) */
 void oss_conv1x1_set_wg(int on, int pixels);
 void oss_conv1x1_wgrad_set_tile(int mode);
-/* pixels per partial product of the GROUPED weight-gradient launch (oss_flush_wgrads), in units of 512: default 4 (env
- * VMAMBAIR_WGRAD_SPAN); 1 reproduces the one-problem launches bit for bit, larger values write fewer partial vectors */
+/* pixels per partial product of the GROUPED weight-gradient launch (oss_flush_wgrads), in units of 512: the library starts at 4;
+ * 1 reproduces the one-problem launches bit for bit, larger values write fewer partial vectors */
 void oss_conv1x1_wgrad_set_span(int mult);
 int oss_conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dweight, float *dbias, float *partials, int batch,
                       int cout, int cin, int pixels, int64_t dy_batch_stride, int64_t dy_channel_stride,

@@ -277,3 +277,34 @@ def test_shape_rules_of_the_fused_kernels_are_pure_host_queries():
     n = lib.oss_conv1x1_dgrad_ln_bwd_partial_floats(8, 96, 4096)
     assert n == 8 * (4096 // 64) * 2 * 96
     assert lib.oss_conv1x1_dgrad_ln_bwd_partial_floats(0, 96, 4096) == 0
+
+
+# every *_ok query that takes an oss_dtype, with arguments one of the element types answers 1 for
+_DTYPE_PREDICATES = {
+    "oss_scan_fused_dt_ok": (2, 96, 38, 6, 16, 4096),
+    "oss_dwconv3x3_fused_ok": (64, 64, 1),
+    "oss_dwgate_fwd_ok": (64, 64),
+    "oss_effn_fwd_ok": (48, 127, 64, 64),
+    "oss_dwconv3x3_flat2_ok": (64, 64),
+    "oss_ln_conv1x1_ok": (192, 96, 4096),
+    "oss_conv1x1_dgrad_ln_bwd_ok": (192, 96, 4096, 8),
+    "oss_proj_rows_optional_ok": (2, 96, 38, 6, 4096),
+    "oss_conv3x3_thin_ok": (3, 48, 16, 16),
+    "oss_conv3x3_dense_ok": (32, 24, 8, 8),
+    "oss_image_metrics_ok": (3, 32, 32, 4, 0),
+}
+
+
+def test_dtype_predicates_refuse_what_is_no_element_type():
+    """one decoder of ``oss_dtype`` (``io_dispatch`` in csrc/oss_host.h): ``OSS_F32_BF16X3`` (3, a selector of the six GEMM-shaped
+    entry points) and an out-of-range value (7) are no element type to any ``*_ok`` query -- none reads them as a 16-bit type"""
+    lib = _capi.load()
+    hdr = _stripped_header()
+    declared = set(re.findall(r"\bint\s+(oss_\w+_ok)\s*\(\s*oss_dtype\b", hdr))
+    assert declared == set(_DTYPE_PREDICATES), declared ^ set(_DTYPE_PREDICATES)
+    assert _capi.OSS_F32_BF16X3 == 3
+    for name, args in _DTYPE_PREDICATES.items():
+        fn = getattr(lib, name)
+        assert fn(_capi.OSS_BF16, *args) == 1, name      # the arguments are a shape the query takes ...
+        assert fn(3, *args) == 0 and fn(7, *args) == 0, name   # ... so the 0 is the dtype's
+        assert fn(-1, *args) == 0, name

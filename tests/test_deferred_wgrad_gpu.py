@@ -18,7 +18,6 @@ plain float32 on the CPU (``torch.einsum``: an unrelated summation order), and t
 (three fp32 blockings of 7800 terms differ by less than 1.5 x among themselves; one lost pixel is four orders of magnitude more).
 The measured ratio is printed (``pytest -s`` / the captured output of a failure)."""
 import functools
-import os
 
 import pytest
 import torch
@@ -43,7 +42,7 @@ def _stream():
 
 
 def _restore_span():
-    _lib().oss_conv1x1_wgrad_set_span(int(os.environ.get("VMAMBAIR_WGRAD_SPAN", "4")))
+    _lib().oss_conv1x1_wgrad_set_span(4)   # the library's start value
 
 
 def _flush():

@@ -604,6 +604,21 @@ def test_csrc_has_no_compile_time_switches():
         assert not re.search(r"OSS_EXP_|OSS_WITHOUT_", open(f).read()), f
 
 
+def test_csrc_reads_no_environment():
+    """Nothing under ``vmambair_amd/csrc/`` reads the process environment: what a call launches depends on its arguments and on the
+    documented setters (``oss_conv1x1_set_wg``, ``oss_conv1x1_wgrad_set_tile`` / ``_set_span``, ``oss_proj_set_path``,
+    ``oss_scan_set_*``) alone, so a stray variable in a job's environment cannot change the launch shapes, and no kernel is reachable
+    only through one.  An A-B of another form is a second worktree (``VMAMBAIR_LIB``), as for the compile-time switches above."""
+    import glob
+    import os
+    import re
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vmambair_amd")
+    csrc = sorted(f for f in glob.glob(os.path.join(pkg, "csrc", "**"), recursive=True) if os.path.isfile(f))
+    assert len(csrc) > 20
+    for f in csrc:
+        assert not re.search(r"getenv|environ", open(f).read()), f
+
+
 def test_scan_has_one_host_boundary():
     """the compiled layer (csrc_host/oss_torch_host.cpp) is the only code that fills the scan's parameter structs and calls the
     C ABI's scan entry points: ``ops/scan.py`` holds no second copy, and nothing selects between boundaries"""

@@ -1,6 +1,5 @@
 // oss_capi.hip -- the extern "C" surface declared in include/vmambair_oss.h.
 #include <atomic>
-#include <cstdlib>
 #include <mutex>
 #include <vector>
 #include <cstring>
@@ -199,10 +198,9 @@ static const char *const kFamKernels[FAM_N] = {"oss_conv1x1_pair_kernel|oss_conv
 static std::atomic<int> g_fam_on{0};
 static double g_fam_bytes[FAM_N];
 static long long g_fam_calls[FAM_N];
-static inline int esz(oss_dtype io) { return io == OSS_F32 ? 4 : 2; }
 // OSS_F32_BF16X3 is a per-call selector, not an element type: the six entry points that accept it turn it into OSS_F32 plus a flag
-// before anything looks at `io` (esz() above and most dispatchers read every value that is not OSS_F32 as a 2-byte type)
-// (every OTHER entry point with an oss_dtype argument opens with `if (is_f32_split(io)) return <its dtype error>;`)
+// before anything looks at `io`.  Every launcher decodes `io` with io_dispatch (oss_host.h), which refuses it like any other value
+// that is no element type; the guards below only keep such a call out of the family counters and in front of the null checks.
 static inline bool is_f32_split(oss_dtype io) { return io == OSS_F32_BF16X3; }
 static inline int take_f32_split(oss_dtype &io) {
     if (!is_f32_split(io)) return 0;
@@ -263,12 +261,12 @@ int oss_scan_chunk(void) { return kScanChunk; }
 int oss_scan_num_chunks(int seqlen) { return seqlen <= 0 ? 0 : (seqlen + kScanChunk - 1) / kScanChunk; }
 
 int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream) {
-    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    const int eb = io_bytes(io);
+    if (!eb) return OSS_ERR_SHAPE;
     int rc = check_fwd(p);
     if (rc != OSS_OK) return rc;
     if (!p->out || !p->x) return OSS_ERR_NULL;
     if (p->batch == 0 || p->seqlen == 0) return OSS_OK;
-    const int eb = io == OSS_F32 ? 4 : 2;
     // per-call fields (oss_scan_fwd_params.tune_*) win over the process-global test overrides; 0 / -1 = heuristic
     int v = p->tune_variant > 0 ? p->tune_variant - 1 : g_force_fwd.load();
     if (v < 0) v = scan_fwd_pick_variant(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, eb);
@@ -278,12 +276,7 @@ int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfTimer prof(0, v, (int)io, fwd_alg_bytes(*p, eb), fwd_own_bytes(*p, eb));
     prof.begin(s);
-    switch (io) {
-        case OSS_F32: rc = scan_fwd_dispatch<float>(*p, v, sr, s); break;
-        case OSS_F16: rc = scan_fwd_dispatch<f16_t>(*p, v, sr, s); break;
-        case OSS_BF16: rc = scan_fwd_dispatch<bf16_t>(*p, v, sr, s); break;
-        default: rc = OSS_ERR_SHAPE;
-    }
+    rc = io_dispatch(io, [&](auto tag) { return scan_fwd_dispatch<typename decltype(tag)::type>(*p, v, sr, s); });
     if (g_last_fwd_segments.load() > 1) prof.segmented();   // local pass + real pass: timed as one call, in its own bucket
     prof.end(s);
     return rc;
@@ -324,7 +317,8 @@ size_t oss_scan_fwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, 
 int oss_scan_bwd_finish_dt_ok(int seqlen, int dt_rank) { return scan_finish_dt_ok(seqlen, dt_rank) ? 1 : 0; }
 
 int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream) {
-    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    const int eb = io_bytes(io);
+    if (!eb) return OSS_ERR_SHAPE;
     if (!p) return OSS_ERR_NULL;
     int rc = check_fwd(&p->f);
     if (rc != OSS_OK) return rc;
@@ -338,25 +332,18 @@ int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream
     const int v = bwd_variant_for(f.batch, f.dim, f.seqlen, f.dstate, f.n_groups, p->tune_variant);
     g_last_bwd.store(v);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int eb = io == OSS_F32 ? 4 : 2;
     ProfTimer prof(1, v, (int)io, bwd_alg_bytes(f, eb), bwd_own_bytes(*p, eb));
     ProfTimer fprof(2, v, (int)io, 0.0);   // the finishing kernel of the same call
     const int sr = p->tune_segments > 0 ? p->tune_segments : g_force_bwd_seg.load();
     g_last_bwd_lane_states.store(0);
-    switch (io) {
-        case OSS_F32: return scan_bwd_dispatch<float>(*p, v, sr, s, &prof, &fprof);
-        case OSS_F16: return scan_bwd_dispatch<f16_t>(*p, v, sr, s, &prof, &fprof);
-        case OSS_BF16: return scan_bwd_dispatch<bf16_t>(*p, v, sr, s, &prof, &fprof);
-        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
-    }
-    return OSS_ERR_SHAPE;
+    return io_dispatch(io, [&](auto tag) { return scan_bwd_dispatch<typename decltype(tag)::type>(*p, v, sr, s, &prof, &fprof); });
 }
 
 int oss_dwconv3x3_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, void *pre_silu, int batch,
                       int channels, int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, int flip,
                       oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * (pre_silu ? 3.0 : 2.0) + 40.0 * channels);
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * (pre_silu ? 3.0 : 2.0) + 40.0 * channels);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3(io, x, weight, bias, y, batch, channels, height, width, xsb, xsc, ysb, ysc, flip,
@@ -364,14 +351,13 @@ int oss_dwconv3x3_fwd(oss_dtype io, const void *x, const float *weight, const fl
 }
 
 int oss_dwconv3x3_fused_ok(oss_dtype io, int height, int width, int channels_per_workgroup) {
-    if (is_f32_split(io)) return 0;
     return dwconv3x3_fused_ok(io, height, width, channels_per_workgroup);
 }
 
 int oss_dwconv3x3_silu_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int channels,
                            int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 2.0 + 40.0 * channels);
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * 2.0 + 40.0 * channels);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3(io, x, weight, bias, y, batch, channels, height, width, xsb, xsc, ysb, ysc, 0,
@@ -382,7 +368,7 @@ int oss_dwconv3x3_silu_bwd(oss_dtype io, const void *x, const float *weight, con
                            float *dweight, float *dbias, float *partials, int batch, int channels, int height, int width,
                            int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + 80.0 * channels);
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * 3.0 + 80.0 * channels);
     if (!x || !weight || !dy || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3_bwd_fused(io, 0, x, weight, bias, dy, dx, dweight, dbias, partials, batch, channels, height, width, xsb, xsc,
@@ -390,14 +376,13 @@ int oss_dwconv3x3_silu_bwd(oss_dtype io, const void *x, const float *weight, con
 }
 
 int oss_dwconv3x3_flat2_ok(oss_dtype io, int height, int width) {
-    if (is_f32_split(io)) return 0;
     return dwconv3x3_flat2_ok(io, height, width);
 }
 
 int oss_dwconv3x3_silu_flat2_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *x2, int batch, int channels,
                                  int height, int width, int64_t xsb, int64_t xsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + 40.0 * channels);
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * 3.0 + 40.0 * channels);
     if (!x || !weight || !x2) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3_silu_flat2_fwd(io, x, weight, bias, x2, batch, channels, height, width, xsb, xsc, reinterpret_cast<hipStream_t>(stream));
@@ -407,7 +392,7 @@ int oss_dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *weigh
                                  float *dweight, float *dbias, float *partials, int batch, int channels, int height, int width,
                                  int64_t xsb, int64_t xsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 4.0 + 80.0 * channels);
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * 4.0 + 80.0 * channels);
     if (!x || !weight || !g2 || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || channels > 65535 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3_silu_flat2_bwd(io, x, weight, bias, g2, dx, dweight, dbias, partials, batch, channels, height, width, xsb, xsc, dsb,
@@ -415,7 +400,6 @@ int oss_dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *weigh
 }
 
 int oss_effn_fwd_ok(oss_dtype io, int channels, int hidden, int height, int width) {
-    if (is_f32_split(io)) return 0;
     return effn_fwd_ok(io, channels, hidden, height, width);
 }
 
@@ -430,7 +414,7 @@ int oss_effn_fwd(oss_dtype io, const void *x, const float *norm_weight, const fl
                  const void *w_out, void *out, int batch, int channels, int hidden, int height, int width, int64_t xsb, int64_t xsc,
                  int64_t osb, int64_t osc, float eps, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * 3.0 + (double)hidden * (3.0 * channels * esz(io) + 72.0));
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * 3.0 + (double)hidden * (3.0 * channels * io_bytes(io) + 72.0));
     if (!x || !norm_weight || !w_in || !w_dw || !w_out || !out) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || hidden <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
     return effn_fwd(io, x, norm_weight, norm_bias, w_in, w_dw, w_out, out, batch, channels, hidden, height, width, xsb, xsc, osb, osc, eps,
@@ -438,14 +422,13 @@ int oss_effn_fwd(oss_dtype io, const void *x, const float *norm_weight, const fl
 }
 
 int oss_dwgate_fwd_ok(oss_dtype io, int height, int width) {
-    if (is_f32_split(io)) return 0;
     return dwgate_fwd_ok(io, height, width);
 }
 
 int oss_dwgate_fwd(oss_dtype io, const void *t, const float *weight, const float *bias, void *out, int batch, int hidden,
                    int height, int width, int64_t tsb, int64_t tsc, int64_t osb, int64_t osc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * hidden * height * width * esz(io) * 3.0 + 80.0 * hidden);
+    fam_count(FAM_DWCONV, (double)batch * hidden * height * width * io_bytes(io) * 3.0 + 80.0 * hidden);
     if (!t || !weight || !out) return OSS_ERR_NULL;
     if (batch <= 0 || hidden <= 0 || height <= 0 || width <= 0 || hidden > 32767 || batch > 65535) return OSS_ERR_SHAPE;
     return dwgate_fwd(io, t, weight, bias, out, batch, hidden, height, width, tsb, tsc, osb, osc, reinterpret_cast<hipStream_t>(stream));
@@ -455,7 +438,7 @@ int oss_dwgate_bwd(oss_dtype io, const void *t, const float *weight, const float
                    float *dweight, float *dbias, float *partials, int batch, int hidden, int height, int width, int64_t tsb,
                    int64_t tsc, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * hidden * height * width * esz(io) * 5.0 + 160.0 * hidden);
+    fam_count(FAM_DWCONV, (double)batch * hidden * height * width * io_bytes(io) * 5.0 + 160.0 * hidden);
     if (!t || !weight || !dout || !dt || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || hidden <= 0 || height <= 0 || width <= 0 || hidden > 32767 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3_bwd_fused(io, 1, t, weight, bias, dout, dt, dweight, dbias, partials, batch, 2 * hidden, height, width, tsb,
@@ -466,7 +449,7 @@ int oss_dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dwei
                         const void *pre_silu, void *dpre, int batch, int channels, int height, int width, int64_t xsb,
                         int64_t xsc, int64_t gsb, int64_t gsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_DWCONV, (double)batch * channels * height * width * esz(io) * (pre_silu ? 4.0 : 2.0));
+    fam_count(FAM_DWCONV, (double)batch * channels * height * width * io_bytes(io) * (pre_silu ? 4.0 : 2.0));
     if (!x || !dy || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return dwconv3x3_wgrad(io, x, dy, dweight, dbias, partials, batch, channels, height, width, xsb, xsc, gsb, gsc,
@@ -476,7 +459,7 @@ int oss_dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dwei
 int oss_conv1x1_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, const void *residual, void *y,
                     int batch, int cout, int cin, int pixels, int64_t xsb, int64_t xsc, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout + (residual ? cout : 0)) + 4.0 * cin * cout);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * io_bytes(io) * ((double)cin + cout + (residual ? cout : 0)) + 4.0 * cin * cout);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535 || cout > 32 * 65535) return OSS_ERR_SHAPE;
     return conv1x1(io, x, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, cin, 1, reinterpret_cast<hipStream_t>(stream),
@@ -486,7 +469,7 @@ int oss_conv1x1_fwd(oss_dtype io, const void *x, const float *weight, const floa
 int oss_conv1x1_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cout, int cin, int pixels,
                       int64_t gsb, int64_t gsc, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * io_bytes(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!dy || !weight || !dx) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     // dx[ci] = sum_co W[co][ci] dy[co]: the same GEMM with the weights read transposed
@@ -501,7 +484,7 @@ size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels
 int oss_conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dweight, float *dbias, float *partials, int batch,
                       int cout, int cin, int pixels, int64_t gsb, int64_t gsc, int64_t xsb, int64_t xsc, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_WGRAD, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
+    fam_count(FAM_WGRAD, (double)batch * pixels * io_bytes(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!dy || !x || !dweight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return conv1x1_wgrad(io, dy, x, dweight, partials, batch, cout, cin, pixels, gsb, gsc, xsb, xsc,
@@ -519,7 +502,7 @@ size_t oss_proj_wgrad_partial_floats(int batch, int D, int C, int R, int seqlen)
 int oss_proj_fwd(oss_dtype io, const void *x2, const float *x_proj_weight, const float *dt_projs_weight, void *xdbl, void *dts,
                  int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_PROJ, (double)batch * seqlen * esz(io) * (2.0 * D + 4.0 * C + (dts ? 4.0 * R + 4.0 * D : 0.0)) + 16.0 * C * D + 16.0 * D * R);
+    fam_count(FAM_PROJ, (double)batch * seqlen * io_bytes(io) * (2.0 * D + 4.0 * C + (dts ? 4.0 * R + 4.0 * D : 0.0)) + 16.0 * C * D + 16.0 * D * R);
     if (!x2 || !x_proj_weight || !dt_projs_weight || !xdbl) return OSS_ERR_NULL;   // dts == NULL: fused-delta form
     if (batch <= 0 || D <= 0 || seqlen <= 0 || R <= 0 || C <= R) return OSS_ERR_SHAPE;
     return proj_fwd(io, x2, x_proj_weight, dt_projs_weight, xdbl, dts, batch, D, C, R, seqlen, reinterpret_cast<hipStream_t>(stream), x3);
@@ -528,7 +511,7 @@ int oss_proj_fwd(oss_dtype io, const void *x2, const float *x_proj_weight, const
 int oss_proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, const float *x_proj_weight,
                    const float *dt_projs_weight, void *dx2, int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_PROJ, (double)batch * seqlen * esz(io) * ((ddts ? 4.0 * D + 4.0 * R : 0.0) + 4.0 * C + (du ? 4.0 * D : 0.0) + 2.0 * D) + 16.0 * C * D);
+    fam_count(FAM_PROJ, (double)batch * seqlen * io_bytes(io) * ((ddts ? 4.0 * D + 4.0 * R : 0.0) + 4.0 * C + (du ? 4.0 * D : 0.0) + 2.0 * D) + 16.0 * C * D);
     if (!dxdbl || !x_proj_weight || !dt_projs_weight || !dx2) return OSS_ERR_NULL;   // ddts == NULL: fused-delta form
     if (batch <= 0 || D <= 0 || seqlen <= 0 || R <= 0 || C <= R) return OSS_ERR_SHAPE;
     return proj_dgrad(io, ddts, dxdbl, du, x_proj_weight, dt_projs_weight, dx2, batch, D, C, R, seqlen,
@@ -537,27 +520,22 @@ int oss_proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, 
 
 void oss_proj_set_path(int force_vector_alu) { proj_force_valu(force_vector_alu); }
 int oss_proj_rows_optional_ok(oss_dtype io, int batch, int D, int C, int R, int seqlen) {
-    if (is_f32_split(io)) return 0;
     return proj_mfma_ok(io, batch, D, C, R, seqlen) ? 1 : 0;
 }
 int oss_scan_fused_dt_ok(oss_dtype io, int batch, int D, int C, int R, int dstate, int seqlen) {
-    if (is_f32_split(io)) return 0;
     return proj_mfma_ok(io, batch, D, C, R, seqlen) && R >= 1 && R <= kMaxDtRank && dstate <= 64 && seqlen >= 512;
 }
 int oss_conv1x1_wg(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cout, int cin,
                    int pixels, int64_t xsb, int64_t xsc, int transposed_weight, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV1X1, (double)batch * pixels * esz(io) * ((double)cin + cout) + 4.0 * cin * cout);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * io_bytes(io) * ((double)cin + cout) + 4.0 * cin * cout);
     if (!x || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return conv1x1_wg(io, x, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, transposed_weight, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oss_ln_conv1x1_ok(oss_dtype io, int cout, int cin, int pixels) {
-    if (is_f32_split(io)) return 0;
-    static const float dummy = 0.f;   // shape / dtype rules only: an aligned stand-in for the pointers
-    const void *a = reinterpret_cast<const void *>(uintptr_t(256));
-    (void)dummy;
+    const void *a = reinterpret_cast<const void *>(uintptr_t(256));   // shape / dtype rules only: an aligned stand-in for the pointers
     return conv1x1_wg_ok(io, cout, cin, pixels, (int64_t)cin * pixels, pixels, a, a, reinterpret_cast<const float *>(a), nullptr);
 }
 
@@ -565,7 +543,7 @@ int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, cons
                        float *rstd, const float *weight, const float *bias, void *y, int batch, int cout, int cin, int pixels,
                        int64_t xsb, int64_t xsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV1X1, (double)batch * pixels * (esz(io) * (2.0 * cin + cout) + 8.0) + 4.0 * cin * cout);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * (io_bytes(io) * (2.0 * cin + cout) + 8.0) + 4.0 * cin * cout);
     if (!x || !ln_weight || !n || !mean || !rstd || !weight || !y) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return ln_conv1x1_wg(io, x, ln_weight, ln_bias, eps, n, mean, rstd, weight, bias, y, batch, cout, cin, pixels, xsb, xsc,
@@ -573,7 +551,6 @@ int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, cons
 }
 
 int oss_conv1x1_dgrad_ln_bwd_ok(oss_dtype io, int cout, int cin, int pixels, int batch) {
-    if (is_f32_split(io)) return 0;
     return conv1x1_dgrad_lnbwd_ok(io, cin, cout, pixels, batch);
 }
 size_t oss_conv1x1_dgrad_ln_bwd_partial_floats(int batch, int cin, int pixels) {
@@ -584,7 +561,7 @@ int oss_conv1x1_dgrad_ln_bwd(oss_dtype io, const void *dy, const float *weight, 
                              const float *mean, const float *rstd, const void *skip_grad, void *dx, float *dln_weight, float *dln_bias,
                              float *partials, int batch, int cout, int cin, int pixels, int64_t gsb, int64_t gsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV1X1, (double)batch * pixels * (esz(io) * ((double)cout + 2.0 * cin + (skip_grad ? cin : 0)) + 8.0) + 4.0 * cin * cout);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * (io_bytes(io) * ((double)cout + 2.0 * cin + (skip_grad ? cin : 0)) + 8.0) + 4.0 * cin * cout);
     if (!dy || !weight || !x || !ln_weight || !mean || !rstd || !dx || !dln_weight || !partials) return OSS_ERR_NULL;
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return conv1x1_dgrad_lnbwd(io, dy, weight, x, ln_weight, ln_has_bias, mean, rstd, skip_grad, dx, dln_weight, dln_bias, partials, batch,
@@ -598,7 +575,7 @@ void oss_conv1x1_wgrad_set_span(int mult) { conv1x1_wgrad_set_span(mult); }
 int oss_proj_wgrad(oss_dtype io, const void *x2, const void *xdbl, const void *dxdbl, const void *ddts, float *dx_proj_weight,
                    float *ddt_projs_weight, float *partials, int batch, int D, int C, int R, int seqlen, oss_stream_t stream) {
     const int x3 = take_f32_split(io);   // OSS_F32_BF16X3 -> OSS_F32 + flag
-    fam_count(FAM_WGRAD, (double)batch * seqlen * esz(io) * (2.0 * D + 8.0 * C + (ddts ? 4.0 * D : 0.0)));
+    fam_count(FAM_WGRAD, (double)batch * seqlen * io_bytes(io) * (2.0 * D + 8.0 * C + (ddts ? 4.0 * D : 0.0)));
     if (!x2 || !xdbl || !dxdbl || !dx_proj_weight || !partials) return OSS_ERR_NULL;
     if (ddts && !ddt_projs_weight) return OSS_ERR_NULL;   // ddts == NULL: the scan backward produced ddt_projs_weight itself
     if (batch <= 0 || D <= 0 || seqlen <= 0 || R <= 0 || C <= R) return OSS_ERR_SHAPE;
@@ -627,7 +604,7 @@ int oss_proj_wgrad(oss_dtype io, const void *x2, const void *xdbl, const void *d
 int oss_cross_scan2(oss_dtype in_type, oss_dtype out_type, const void *x, void *x2, int batch, int D, int height, int width,
                     int64_t x_batch_stride, int64_t x_channel_stride, oss_stream_t stream) {
     if (is_f32_split(in_type) || is_f32_split(out_type)) return OSS_ERR_SHAPE;
-    fam_count(FAM_MERGE, (double)batch * D * height * width * (esz(in_type) + 2.0 * esz(out_type)));
+    fam_count(FAM_MERGE, (double)batch * D * height * width * (io_bytes(in_type) + 2.0 * io_bytes(out_type)));
     if (!x || !x2) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
     return cross_scan2(in_type, out_type, x, x2, batch, D, height, width, x_batch_stride, x_channel_stride,
@@ -636,7 +613,7 @@ int oss_cross_scan2(oss_dtype in_type, oss_dtype out_type, const void *x, void *
 
 int oss_cross_merge2(oss_dtype io, const void *g2, void *dx, int batch, int D, int height, int width, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_MERGE, (double)batch * D * height * width * esz(io) * 3.0);
+    fam_count(FAM_MERGE, (double)batch * D * height * width * io_bytes(io) * 3.0);
     if (!g2 || !dx) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0) return OSS_ERR_SHAPE;
     return cross_merge2(io, g2, dx, batch, D, height, width, reinterpret_cast<hipStream_t>(stream));
@@ -660,7 +637,7 @@ int oss_chan_bwd(const oss_chan_params *p, const float *gc, float *dpooled, floa
 int oss_rowsum(oss_dtype io, const void *a, const void *bmul, float *out, int batch, int channels, int pixels, int64_t asb,
                int64_t asc, int64_t bsb, int64_t bsc, float alpha, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CHAN, (double)batch * channels * pixels * esz(io) * (bmul ? 2.0 : 1.0));
+    fam_count(FAM_CHAN, (double)batch * channels * pixels * io_bytes(io) * (bmul ? 2.0 : 1.0));
     if (!a || !out) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0) return OSS_ERR_SHAPE;
     return rowsum(io, a, bmul, out, batch, channels, pixels, asb, asc, bsb, bsc, alpha, reinterpret_cast<hipStream_t>(stream));
@@ -669,7 +646,7 @@ int oss_rowsum(oss_dtype io, const void *a, const void *bmul, float *out, int ba
 int oss_row_affine(oss_dtype io, const void *x, const float *mul, const float *add, void *y, int batch, int channels, int pixels,
                    int64_t xsb, int64_t xsc, float alpha, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CHAN, (double)batch * channels * pixels * esz(io) * 2.0);
+    fam_count(FAM_CHAN, (double)batch * channels * pixels * io_bytes(io) * 2.0);
     if (!x || !y) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0) return OSS_ERR_SHAPE;
     return row_affine(io, x, mul, add, y, batch, channels, pixels, xsb, xsc, alpha, reinterpret_cast<hipStream_t>(stream));
@@ -678,7 +655,7 @@ int oss_row_affine(oss_dtype io, const void *x, const float *mul, const float *a
 int oss_gelu_gate_fwd(oss_dtype io, const void *h, void *out, int batch, size_t half_elems, int64_t h_batch_stride,
                       oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_GATE, (double)batch * half_elems * esz(io) * 3.0);
+    fam_count(FAM_GATE, (double)batch * half_elems * io_bytes(io) * 3.0);
     if (!h || !out) return OSS_ERR_NULL;
     if (batch <= 0 || half_elems == 0) return OSS_ERR_SHAPE;
     return gelu_gate_fwd(io, h, out, batch, half_elems, h_batch_stride, reinterpret_cast<hipStream_t>(stream));
@@ -687,27 +664,26 @@ int oss_gelu_gate_fwd(oss_dtype io, const void *h, void *out, int batch, size_t 
 int oss_gelu_gate_bwd(oss_dtype io, const void *h, const void *dout, void *dh, int batch, size_t half_elems,
                       int64_t h_batch_stride, int64_t dout_batch_stride, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_GATE, (double)batch * half_elems * esz(io) * 5.0);
+    fam_count(FAM_GATE, (double)batch * half_elems * io_bytes(io) * 5.0);
     if (!h || !dout || !dh) return OSS_ERR_NULL;
     if (batch <= 0 || half_elems == 0) return OSS_ERR_SHAPE;
     return gelu_gate_bwd(io, h, dout, dh, batch, half_elems, h_batch_stride, dout_batch_stride, reinterpret_cast<hipStream_t>(stream));
 }
 
 int oss_conv3x3_thin_ok(oss_dtype io, int cin, int cout, int height, int width) {
-    if (is_f32_split(io)) return 0;
     return conv3x3_thin_ok(io, cin, cout, height, width);
 }
 int oss_conv3x3_thin_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cin, int cout,
                          int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
+    fam_count(FAM_CONV3X3, (double)batch * height * width * io_bytes(io) * ((double)cin + cout));
     if (!x || !weight || !y) return OSS_ERR_NULL;
     return conv3x3_thin_fwd(io, x, weight, bias, y, batch, cin, cout, height, width, xsb, xsc, ysb, ysc, reinterpret_cast<hipStream_t>(stream));
 }
 int oss_conv3x3_thin_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cin, int cout, int height,
                            int width, int64_t gsb, int64_t gsc, int64_t dsb, int64_t dsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
+    fam_count(FAM_CONV3X3, (double)batch * height * width * io_bytes(io) * ((double)cin + cout));
     if (!dy || !weight || !dx) return OSS_ERR_NULL;
     return conv3x3_thin_dgrad(io, dy, weight, dx, batch, cin, cout, height, width, gsb, gsc, dsb, dsc, reinterpret_cast<hipStream_t>(stream));
 }
@@ -717,19 +693,18 @@ size_t oss_conv3x3_thin_wgrad_partial_floats(int batch, int cin, int cout) {
 int oss_conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *dweight, float *dbias, float *partial, int batch, int cin,
                            int cout, int height, int width, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_CONV3X3, (double)batch * height * width * esz(io) * ((double)cin + cout));
+    fam_count(FAM_CONV3X3, (double)batch * height * width * io_bytes(io) * ((double)cin + cout));
     if (!x || !dy || !dweight || !partial) return OSS_ERR_NULL;
     return conv3x3_thin_wgrad(io, x, dy, dweight, dbias, partial, batch, cin, cout, height, width, xsb, xsc, gsb, gsc,
                               reinterpret_cast<hipStream_t>(stream));
 }
 
 int oss_conv3x3_dense_ok(oss_dtype io, int cin, int cout, int height, int width) {
-    if (is_f32_split(io)) return 0;
     return conv3x3_dense_ok(io, cin, cout, height, width);
 }
 // algorithmic bytes of one call: both activation tensors once, the fp32 weights once
 static double dense_bytes(oss_dtype io, int batch, int cin, int cout, int height, int width) {
-    return (double)batch * height * width * esz(io) * ((double)cin + cout) + 36.0 * cin * cout;
+    return (double)batch * height * width * io_bytes(io) * ((double)cin + cout) + 36.0 * cin * cout;
 }
 int oss_conv3x3_dense_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, int batch, int cin, int cout,
                           int height, int width, int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, oss_stream_t stream) {
@@ -761,7 +736,6 @@ int oss_conv3x3_dense_wgrad(oss_dtype io, const void *x, const void *dy, float *
 }
 
 int oss_image_metrics_ok(oss_dtype io, int channels, int height, int width, int crop_border, int flags) {
-    if (is_f32_split(io)) return 0;
     return image_metrics_ok(io, channels, height, width, crop_border, flags);
 }
 size_t oss_image_metrics_partial_doubles(int batch, int channels, int height, int width, int crop_border) {
@@ -882,7 +856,7 @@ int oss_adamw_ema_step(const oss_adam_chunk *chunks, int n_chunks, float *state,
 
 int oss_merge4(oss_dtype io, const void *out, float *y, int batch, int D, int height, int width, oss_stream_t stream) {
     if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    fam_count(FAM_MERGE, (double)batch * D * height * width * (4.0 * esz(io) + 4.0));
+    fam_count(FAM_MERGE, (double)batch * D * height * width * (4.0 * io_bytes(io) + 4.0));
     if (!out || !y) return OSS_ERR_NULL;
     if (batch <= 0 || D <= 0 || height <= 0 || width <= 0 || (long)batch * D > 65535) return OSS_ERR_SHAPE;
     return merge4(io, out, y, batch, D, height, width, reinterpret_cast<hipStream_t>(stream));
@@ -892,7 +866,7 @@ int oss_ln_nchw_fwd(oss_dtype xt, oss_dtype yt, const void *x, const float *weig
                     void *y, float *mean, float *rstd, int batch, int channels, int pixels, int64_t xsb, int64_t xsc,
                     int64_t gsb, int64_t gsc, float eps, oss_stream_t stream) {
     if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
-    fam_count(FAM_LN, (double)batch * channels * pixels * (esz(xt) + esz(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
+    fam_count(FAM_LN, (double)batch * channels * pixels * (io_bytes(xt) + io_bytes(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
     if (!x || !weight || !y || !mean || !rstd) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return ln_nchw_fwd(xt, yt, x, weight, bias, gate, y, mean, rstd, batch, channels, pixels, xsb, xsc, gsb, gsc, eps,
@@ -908,7 +882,7 @@ int oss_ln_nchw_fwd_pool(oss_dtype xt, oss_dtype yt, const void *x, const float 
                          float *mean, float *rstd, float *pool_part, int batch, int channels, int pixels, int64_t xsb, int64_t xsc,
                          int64_t gsb, int64_t gsc, float eps, oss_stream_t stream) {
     if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
-    fam_count(FAM_LN, (double)batch * channels * pixels * (esz(xt) + esz(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
+    fam_count(FAM_LN, (double)batch * channels * pixels * (io_bytes(xt) + io_bytes(yt) * (gate ? 2.0 : 1.0)) + 8.0 * batch * pixels);
     if (!x || !weight || !y || !mean || !rstd || !pool_part) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535 || channels > 4096) return OSS_ERR_SHAPE;
     return ln_nchw_fwd(xt, yt, x, weight, bias, gate, y, mean, rstd, batch, channels, pixels, xsb, xsc, gsb, gsc, eps,
@@ -920,7 +894,7 @@ int oss_ln_nchw_bwd(oss_dtype xt, oss_dtype yt, const void *x, const float *weig
                     float *dbias, float *partials, const void *skip_grad, int batch, int channels, int pixels, int64_t xsb,
                     int64_t xsc, int64_t gsb, int64_t gsc, int64_t dgate_batch_stride, oss_stream_t stream) {
     if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
-    fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * esz(xt) + esz(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
+    fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * io_bytes(xt) + io_bytes(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
     if (!x || !weight || !dy || !mean || !rstd || !dx || !dweight || !partials) return OSS_ERR_NULL;
     if (gate && !dgate) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535 || channels > 4096) return OSS_ERR_SHAPE;
@@ -935,7 +909,7 @@ int oss_ln_nchw_bwd_affine(oss_dtype xt, oss_dtype yt, const void *x, const floa
                            int channels, int pixels, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc,
                            int64_t dgate_batch_stride, oss_stream_t stream) {
     if (is_f32_split(xt) || is_f32_split(yt)) return OSS_ERR_SHAPE;
-    fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * esz(xt) + esz(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
+    fam_count(FAM_LN, (double)batch * channels * pixels * (2.0 * io_bytes(xt) + io_bytes(yt) * (1.0 + (gate ? 2.0 : 0.0) + (skip_grad ? 1.0 : 0.0))) + 8.0 * batch * pixels);
     if (!x || !weight || !dy || !mean || !rstd || !dx || !dweight || !partials || !dy_add) return OSS_ERR_NULL;
     if (gate && !dgate) return OSS_ERR_NULL;
     if (batch <= 0 || channels <= 0 || pixels <= 0 || batch > 65535 || channels > 4096) return OSS_ERR_SHAPE;
@@ -977,7 +951,6 @@ void oss_prof_reset(void) {
 
 int oss_prof_collect2(int which, int variant, oss_dtype io, double *total_ms, long long *launches, double *algorithmic_bytes,
                       double *own_bytes) {
-    if (is_f32_split(io)) return OSS_ERR_SHAPE;
     const int rc = oss_prof_collect(which, variant, io, total_ms, launches, algorithmic_bytes);
     if (rc == OSS_OK && own_bytes) {
         std::lock_guard<std::mutex> lk(g_prof_mu);
@@ -987,8 +960,7 @@ int oss_prof_collect2(int which, int variant, oss_dtype io, double *total_ms, lo
 }
 
 int oss_prof_collect(int which, int variant, oss_dtype io, double *total_ms, long long *launches, double *algorithmic_bytes) {
-    if (is_f32_split(io)) return OSS_ERR_SHAPE;
-    if (which < 0 || which > 2 || variant < 0 || variant >= kProfVariants || (int)io < 0 || (int)io > 2) return OSS_ERR_SHAPE;
+    if (which < 0 || which > 2 || variant < 0 || variant >= kProfVariants || !io_ok(io)) return OSS_ERR_SHAPE;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     ProfBucket &b = g_prof[which][variant][(int)io];
     for (auto &pr : b.pending) {
@@ -1020,58 +992,10 @@ int oss_scan_last_lane_states(void) { return g_last_bwd_lane_states.load(); }
 int oss_f32_matmul_modes(void) { return 1 | 2; }
 int oss_scan_features(void) { return OSS_FEATURE_FUSED_DT | OSS_FEATURE_LANE_STATES; }
 
-// copy kernels of oss_hbm_copy.  Default (mode 2): one 16-byte element per lane and a grid as large as the buffer -- the
-// dispatcher streams short workgroups faster than any loop keeps loads in flight: 6.12 TB/s on 1 GiB, against 5.58 for
-// contiguous 32 KiB pieces per workgroup with eight loads in flight (mode 0), 5.55 for one such piece per workgroup (mode 3),
-// 5.23 for sixteen loads in flight (mode 4) and 4.75 for the round-2 kernel (mode 1: grid-stride, nontemporal) --
-// profiles/r03_copy_modes.txt; the guide's measured float4 copy is 6.29.  VMAMBAIR_COPY_MODE selects (A-B runs).
-__global__ void __launch_bounds__(256) oss_copy_pieces_kernel(const f32x4 *src, f32x4 *dst, size_t n_pieces) {
-    constexpr size_t PIECE = 2048;   // 16-byte elements per piece
-    for (size_t pc = blockIdx.x; pc < n_pieces; pc += gridDim.x) {
-        const f32x4 *s = src + pc * PIECE + threadIdx.x;
-        f32x4 *d = dst + pc * PIECE + threadIdx.x;
-        f32x4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = s[k * 256];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) d[k * 256] = v[k];
-    }
-}
-// mode 3: one 32 KiB piece per workgroup, grid = number of pieces (no loop: the dispatcher streams workgroups); mode 4: sixteen
-// loads in flight per lane (64 KiB pieces)
-__global__ void __launch_bounds__(256) oss_copy_piece_per_wg_kernel(const f32x4 *src, f32x4 *dst) {
-    const f32x4 *s = src + (size_t)blockIdx.x * 2048 + threadIdx.x;
-    f32x4 *d = dst + (size_t)blockIdx.x * 2048 + threadIdx.x;
-    f32x4 v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = s[k * 256];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) d[k * 256] = v[k];
-}
-__global__ void __launch_bounds__(256) oss_copy_pieces16_kernel(const f32x4 *src, f32x4 *dst, size_t n_pieces) {
-    constexpr size_t PIECE = 4096;
-    for (size_t pc = blockIdx.x; pc < n_pieces; pc += gridDim.x) {
-        const f32x4 *s = src + pc * PIECE + threadIdx.x;
-        f32x4 *d = dst + pc * PIECE + threadIdx.x;
-        f32x4 v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = s[k * 256];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) d[k * 256] = v[k];
-    }
-}
-__global__ void __launch_bounds__(256) oss_copy_kernel(const f32x4 *src, f32x4 *dst, size_t n) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (; i + 7 * stride < n; i += 8 * stride) {
-        f32x4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = __builtin_nontemporal_load(src + i + k * stride);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) __builtin_nontemporal_store(v[k], dst + i + k * stride);
-    }
-    for (; i < n; i += stride) dst[i] = src[i];
-}
+// the copy kernel of oss_hbm_copy: one 16-byte element per lane and a grid as large as the buffer -- the dispatcher streams short
+// workgroups faster than any loop keeps loads in flight: 6.12 TB/s on 1 GiB, against 5.58 for contiguous 32 KiB pieces per
+// workgroup with eight loads in flight, 5.55 for one such piece per workgroup, 5.23 for sixteen loads in flight and 4.75 for the
+// round-2 kernel (grid-stride, nontemporal) -- profiles/r03_copy_modes.txt; the guide's measured float4 copy is 6.29.
 __global__ void __launch_bounds__(256) oss_copy_flat_kernel(const f32x4 *src, f32x4 *dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) dst[i] = src[i];
@@ -1081,30 +1005,9 @@ int oss_hbm_copy(const void *src, void *dst, size_t n_bytes, oss_stream_t stream
     if (!src || !dst) return OSS_ERR_NULL;
     const size_t n = n_bytes / 16;
     if (n == 0) return OSS_OK;
-    static const int mode = [] { const char *e = std::getenv("VMAMBAIR_COPY_MODE"); return e ? std::atoi(e) : 2; }();
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const f32x4 *sp = reinterpret_cast<const f32x4 *>(src);
-    f32x4 *dp = reinterpret_cast<f32x4 *>(dst);
-    if (mode == 1) {
-        size_t blocks = (n + 255) / 256;
-        if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(oss_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, s, sp, dp, n);
-    } else if (mode == 2 && (n + 255) / 256 <= 0x7fffffffu) {
-        hipLaunchKernelGGL(oss_copy_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sp, dp, n);
-    } else if (mode == 3 && n % 2048 == 0) {
-        hipLaunchKernelGGL(oss_copy_piece_per_wg_kernel, dim3((unsigned)(n / 2048)), dim3(256), 0, s, sp, dp);
-    } else if (mode == 4 && n % 4096 == 0) {
-        hipLaunchKernelGGL(oss_copy_pieces16_kernel, dim3((unsigned)std::min<size_t>(n / 4096, 256 * 4)), dim3(256), 0, s, sp, dp, n / 4096);
-    } else {
-        const size_t pieces = n / 2048, tail = n - pieces * 2048;
-        if (pieces) {
-            const unsigned blocks = (unsigned)std::min<size_t>(pieces, 256 * 8);
-            hipLaunchKernelGGL(oss_copy_pieces_kernel, dim3(blocks), dim3(256), 0, s, sp, dp, pieces);
-        }
-        if (tail)
-            hipLaunchKernelGGL(oss_copy_flat_kernel, dim3((unsigned)((tail + 255) / 256)), dim3(256), 0, s, sp + pieces * 2048,
-                               dp + pieces * 2048, tail);
-    }
+    if ((n + 255) / 256 > 0x7fffffffu) return OSS_ERR_SHAPE;   // over 8 TiB
+    hipLaunchKernelGGL(oss_copy_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const f32x4 *>(src), reinterpret_cast<f32x4 *>(dst), n);
     return (int)hipGetLastError();
 }
 

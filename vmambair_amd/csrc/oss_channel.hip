@@ -749,27 +749,23 @@ size_t chan_bwd_scratch_floats(int B, int L, int dc, int Rc, int Cc) {
 
 int rowsum(oss_dtype io, const void *a, const void *bmul, float *out, int B, int C, int P, int64_t asb, int64_t asc, int64_t bsb,
            int64_t bsc, float alpha, hipStream_t s) {
-    dim3 grid(B * C);
-    switch (io) {
-        case OSS_F32: hipLaunchKernelGGL(oss_rowsum_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(a), reinterpret_cast<const float *>(bmul), out, C, P, asb, asc, bsb, bsc, alpha); break;
-        case OSS_F16: hipLaunchKernelGGL(oss_rowsum_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(a), reinterpret_cast<const f16_t *>(bmul), out, C, P, asb, asc, bsb, bsc, alpha); break;
-        case OSS_BF16: hipLaunchKernelGGL(oss_rowsum_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(a), reinterpret_cast<const bf16_t *>(bmul), out, C, P, asb, asc, bsb, bsc, alpha); break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(oss_rowsum_kernel<T>, dim3(B * C), dim3(256), 0, s, reinterpret_cast<const T *>(a), reinterpret_cast<const T *>(bmul),
+                           out, C, P, asb, asc, bsb, bsc, alpha);
+        return (int)hipGetLastError();
+    });
 }
 
 int row_affine(oss_dtype io, const void *x, const float *mul, const float *add, void *y, int B, int C, int P, int64_t xsb,
                int64_t xsc, float alpha, hipStream_t s) {
-    if ((long)B * C > 65535) return OSS_ERR_SHAPE;
-    dim3 grid((P + 2047) / 2048, B * C);
-    switch (io) {
-        case OSS_F32: hipLaunchKernelGGL(oss_row_affine_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(x), mul, add, reinterpret_cast<float *>(y), C, P, xsb, xsc, alpha); break;
-        case OSS_F16: hipLaunchKernelGGL(oss_row_affine_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(x), mul, add, reinterpret_cast<f16_t *>(y), C, P, xsb, xsc, alpha); break;
-        case OSS_BF16: hipLaunchKernelGGL(oss_row_affine_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(x), mul, add, reinterpret_cast<bf16_t *>(y), C, P, xsb, xsc, alpha); break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if ((long)B * C > 65535) return OSS_ERR_SHAPE;
+        hipLaunchKernelGGL(oss_row_affine_kernel<T>, dim3((P + 2047) / 2048, B * C), dim3(256), 0, s, reinterpret_cast<const T *>(x), mul, add,
+                           reinterpret_cast<T *>(y), C, P, xsb, xsc, alpha);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace oss

@@ -17,7 +17,6 @@
 //     8 two-byte loads per lane, each coalesced over the 32 pixel lanes (64-byte segments).
 //   wgrad: k = pixels, so both operands are 16-byte contiguous loads (dy rows and x rows).
 #include <atomic>
-#include <cstdlib>
 #include "oss_device.h"
 #include "oss_global_ptr.h"
 #include "oss_host.h"
@@ -444,9 +443,8 @@ oss_conv1x1_pair_kernel(const T *__restrict__ x, const float *__restrict__ w, co
 // cycles at 255 -> 96, 26 us for a 23 MB problem).  But the 32 rows of a tile are ONE contiguous, 16-byte-aligned block of 32 K
 // floats (m0 is a multiple of 32): the workgroup copies it with coalesced 16-byte loads, narrows it and scatters it into an LDS
 // image [32][K8 + 8] of T once; all four waves then read their fragments with ds_read_b128.
-// WT (input gradient, W(m, k) = w[k * M + m], M % 4 == 0): the tile is 32 contiguous floats of every row k; a 16-byte chunk holds
-// 4 consecutive m of one k and is scattered down a column of the image.
-template <typename T, bool WT>
+// (The same staging for the input gradient's transposed weights measured slower, 188.0 against 191.0 images/s, and is gone.)
+template <typename T>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_pairw_kernel(const T *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
                          T *__restrict__ y, int M, int K, int P, int64_t xsb, int xsk, const T *__restrict__ res) {
@@ -481,52 +479,37 @@ oss_conv1x1_pairw_kernel(const T *__restrict__ x, const float *__restrict__ w, c
     s16x8 fa[KS], fb[KS];
     load_x(0, fa, fb);   // in flight across the staging
 
-    if constexpr (WT) {   // ---- the tile's weights -> LDS (transposing)
-        const int kr = tid >> 3, m4 = (tid & 7) * 4;          // 32 rows k per pass, 8 chunks of 4 columns m each
-        const int mcl = min(m0 + m4, M - 4);                   // (M % 4 == 0: a chunk is inside the matrix or wholly outside)
-        f32x4 q[NI];
+    // ---- the tile's weights -> LDS
+    // the tile's rows are ONE contiguous block of `have` floats, copied in quads.  When `have` is not a multiple of 4 (odd K with
+    // an odd number of rows in a ragged last tile: K = 193, M = 33) the last quad starts past `lim` and is read `d` elements
+    // EARLIER (clamped address): its values then sit `d` slots further up in the register.  (Round 6: until then they were
+    // stored unshifted and the last 1 - 3 weights of the matrix's last row were wrong -- found by tools/conv_wave_check.py.)
+    const int have = min(M - m0, 32) * K, total = 32 * K, lim = max(have - 4, 0);
+    const float *base = w + (size_t)m0 * K;
+    f32x4 q[NI];
 #pragma unroll
-        for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(w + (size_t)min(kr + 32 * i, K - 1) * M + mcl);
+    for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(base + min(4 * (i * 256 + tid), lim));
+    int r = (4 * tid) / K, k = (4 * tid) - r * K;
+    const int sr = 1024 / K, sk = 1024 - sr * K;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int k = kr + 32 * i;
-            if (k < K) {
+    for (int i = 0; i < NI; ++i) {
+        const int off = 4 * (i * 256 + tid);
+        if (off < total) {
+            const int d = max(off - lim, 0);          // 0 except for the block's last, partial quad (1 .. 3)
+            float v4[4] = {q[i][0], q[i][1], q[i][2], q[i][3]};
+            if (d == 1) { v4[0] = v4[1]; v4[1] = v4[2]; v4[2] = v4[3]; }
+            else if (d == 2) { v4[0] = v4[2]; v4[1] = v4[3]; }
+            else if (d >= 3) { v4[0] = v4[3]; }
+            int rr = r, kk = k;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) wl[(m4 + e) * RS + k] = from_f32<T>(q[i][e]);
+            for (int e = 0; e < 4; ++e) {
+                if (rr < 32 && off + e < have) wl[rr * RS + kk] = from_f32<T>(v4[e]);
+                if (++kk == K) { kk = 0; ++rr; }
             }
         }
-    } else {   // ---- the tile's weights -> LDS
-        // the tile's rows are ONE contiguous block of `have` floats, copied in quads.  When `have` is not a multiple of 4 (odd K with
-        // an odd number of rows in a ragged last tile: K = 193, M = 33) the last quad starts past `lim` and is read `d` elements
-        // EARLIER (clamped address): its values then sit `d` slots further up in the register.  (Round 6: until then they were
-        // stored unshifted and the last 1 - 3 weights of the matrix's last row were wrong -- found by tools/conv_wave_check.py.)
-        const int have = min(M - m0, 32) * K, total = 32 * K, lim = max(have - 4, 0);
-        const float *base = w + (size_t)m0 * K;
-        f32x4 q[NI];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) q[i] = *reinterpret_cast<const f32x4 *>(base + min(4 * (i * 256 + tid), lim));
-        int r = (4 * tid) / K, k = (4 * tid) - r * K;
-        const int sr = 1024 / K, sk = 1024 - sr * K;
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int off = 4 * (i * 256 + tid);
-            if (off < total) {
-                const int d = max(off - lim, 0);          // 0 except for the block's last, partial quad (1 .. 3)
-                float v4[4] = {q[i][0], q[i][1], q[i][2], q[i][3]};
-                if (d == 1) { v4[0] = v4[1]; v4[1] = v4[2]; v4[2] = v4[3]; }
-                else if (d == 2) { v4[0] = v4[2]; v4[1] = v4[3]; }
-                else if (d >= 3) { v4[0] = v4[3]; }
-                int rr = r, kk = k;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (rr < 32 && off + e < have) wl[rr * RS + kk] = from_f32<T>(v4[e]);
-                    if (++kk == K) { kk = 0; ++rr; }
-                }
-            }
-            k += sk;
-            r += sr;
-            if (k >= K) { k -= K; ++r; }
-        }
+        k += sk;
+        r += sr;
+        if (k >= K) { k -= K; ++r; }
     }
     __syncthreads();
     if (!active) return;
@@ -848,16 +831,9 @@ oss_conv1x1_wgrad_finish(const float *__restrict__ part, float *__restrict__ dw,
     }
 }
 
-// how many waves a launch of the whole-K kernels aims for (row tiles are dealt to more workgroups until it is reached);
-// VMAMBAIR_CONV1X1_WAVES overrides for A-B timing
-static long conv1x1_target_waves() {
-    static const long v = [] {
-        const char *e = getenv("VMAMBAIR_CONV1X1_WAVES");
-        const long t = e ? atol(e) : 0;
-        return t > 0 ? t : 1024L;   // 1024 / 2048 / 4096: 177.0 / 176.2 / 175.0 images/s (profiles/r02_conv1x1_pipeline.txt)
-    }();
-    return v;
-}
+// how many waves a launch of the whole-K kernels aims for (row tiles are dealt to more workgroups until it is reached):
+// 1024 / 2048 / 4096: 177.0 / 176.2 / 175.0 images/s (profiles/r02_conv1x1_pipeline.txt)
+constexpr long kConv1x1TargetWaves = 1024;
 
 template <typename T>
 static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, int B, int M, int K, int P, int64_t xsb,
@@ -875,12 +851,12 @@ static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, 
         const int xk = (int)xsk;
         if (plain && !wvec && K > 16 * 3 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0) {
             // forward with rows that are not 16-byte aligned (K = 127, the EFFN hidden width at dim 48): weight tile through LDS
-            hipLaunchKernelGGL((oss_conv1x1_pairw_kernel<T, false>), dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
+            hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
             return;
         }
         if (K <= 16 * 12) {
             // whole K in registers: enough workgroups to fill the chip twice, otherwise as few activation re-loads as possible
-            int split = (int)((conv1x1_target_waves() + waves_p - 1) / waves_p);
+            int split = (int)((kConv1x1TargetWaves + waves_p - 1) / waves_p);
             if (split < 1) split = 1;
             if (split > mt) split = mt;
             const int per = (mt + split - 1) / split;
@@ -901,13 +877,8 @@ static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, 
             int per = 3;
             while (per > 1 && waves_p * ((mt + per - 1) / per) < 4096) --per;
             if (per > mt) per = mt;
-            // forward: weights through LDS.  (The same for the input gradient -- template WT, parity-green -- measured SLOWER,
-            // 188.0 against 191.0 images/s: its element-wise loads are coalesced already (32 consecutive m per k) and the
-            // transposing LDS scatter plus the barrier cost more than they save.  Kept for A-B runs: VMAMBAIR_CONV1X1_WT_LDS=1.)
-            static const bool wt_lds = getenv("VMAMBAIR_CONV1X1_WT_LDS") != nullptr;
-            if (per == 1 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && (plain || (wt && wt_lds && M % 4 == 0))) {
-                if (plain) hipLaunchKernelGGL((oss_conv1x1_pairw_kernel<T, false>), dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
-                else       hipLaunchKernelGGL((oss_conv1x1_pairw_kernel<T, true>), dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
+            if (per == 1 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && plain) {   // forward: weights through LDS
+                hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
                 return;
             }
             dim3 grid(pb, B, (mt + per - 1) / per);
@@ -943,17 +914,8 @@ static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, 
     }
 }
 
-// 0 = never the workgroup-level kernel of oss_conv1x1_wg.hip (A-B timing).  Initial value from VMAMBAIR_CONV1X1_WG (default on).
-static std::atomic<int> g_conv_wg{-1};
-static bool conv_wg_on() {
-    int m = g_conv_wg.load();
-    if (m < 0) {
-        const char *e = std::getenv("VMAMBAIR_CONV1X1_WG");
-        m = (e && std::atoi(e) == 0) ? 0 : 1;
-        g_conv_wg.store(m);
-    }
-    return m != 0;
-}
+// 0 = never the workgroup-level kernel of oss_conv1x1_wg.hip (A-B timing: conv1x1_set_wg)
+static std::atomic<int> g_conv_wg{1};
 
 void conv1x1_set_wg(int on) { g_conv_wg.store(on ? 1 : 0); }
 
@@ -961,30 +923,27 @@ int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void
             int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res, int f32_split) {
     {
         const bool wt = (ws_m == 1 && ws_k == M), plain = (ws_k == 1 && ws_m == K);
-        if ((wt || plain) && conv_wg_on() && conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res))
+        if ((wt || plain) && g_conv_wg.load() != 0 && conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res))
             return conv1x1_wg(io, x, w, bias, y, B, M, K, P, xsb, xsk, wt ? 1 : 0, s, res);
     }
-    switch (io) {
-        case OSS_BF16:
-            conv1x1_launch<bf16_t>(reinterpret_cast<const bf16_t *>(x), w, bias, reinterpret_cast<bf16_t *>(y), B, M, K, P, xsb,
-                                   xsk, ws_m, ws_k, s, reinterpret_cast<const bf16_t *>(res));
-            break;
-        case OSS_F16:
-            conv1x1_launch<f16_t>(reinterpret_cast<const f16_t *>(x), w, bias, reinterpret_cast<f16_t *>(y), B, M, K, P, xsb, xsk,
-                                  ws_m, ws_k, s, reinterpret_cast<const f16_t *>(res));
-            break;
-        default:   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
-            return conv1x1_f32(reinterpret_cast<const float *>(x), w, bias, reinterpret_cast<float *>(y), B, M, K, P, xsb, xsk, ws_m, ws_k,
-                               s, reinterpret_cast<const float *>(res), f32_split);
-    }
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *xp = reinterpret_cast<const T *>(x), *rp = reinterpret_cast<const T *>(res);
+        T *yp = reinterpret_cast<T *>(y);
+        if constexpr (sizeof(T) == 4) {   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
+            return conv1x1_f32(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, f32_split);
+        } else {
+            conv1x1_launch<T>(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp);
+            return (int)hipGetLastError();
+        }
+    });
 }
 
 // The same partial product with TM x TN MFMA tiles (32 TM rows of dW x 32 TN columns) per wave: a wave then reads its 32 TM
 // rows of dy and 32 TN rows of x once for TM TN tiles, so the launch re-reads dy ceil(NB / 32 TN) times and x
 // ceil(M / 32 TM) times instead of ceil(NB / 32) and ceil(M / 32).  The 1 x 1 kernel above moves 22 MB through L2 for the
 // 9.4 MB of a (96 x 48, 8 x 4096 pixels) problem and runs at about the speed that traffic allows; 2 x 2 moves 12.6 MB.
-// OPT-IN (VMAMBAIR_WGRAD_TILE = 12 | 21 | 22) until measured on the box; identical partial layout and finishing.
+// OPT-IN (oss_conv1x1_wgrad_set_tile: 12 | 21 | 22) until measured on the box; identical partial layout and finishing.
 template <typename T, int TM, int TN>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_wgrad_tiles_kernel(const T *__restrict__ dy, const T *__restrict__ x, float *__restrict__ part, int M, int N, int P,
@@ -1117,19 +1076,8 @@ oss_conv1x1_wgrad_tiles_kernel(const T *__restrict__ dy, const T *__restrict__ x
             }
 }
 
-// 0 = the 1 x 1 kernel (default); 12, 21, 22 = TM x TN tiles per wave.  Initial value from VMAMBAIR_WGRAD_TILE,
-// changed at run time by oss_conv1x1_wgrad_set_tile (tests, A-B timing)
-static std::atomic<int> g_wgrad_tile{-1};
-static int wgrad_tile_mode() {
-    int m = g_wgrad_tile.load();
-    if (m < 0) {
-        const char *e = std::getenv("VMAMBAIR_WGRAD_TILE");
-        const int v = e ? std::atoi(e) : 0;
-        m = (v == 12 || v == 21 || v == 22) ? v : 0;
-        g_wgrad_tile.store(m);
-    }
-    return m;
-}
+// 0 = the 1 x 1 kernel (default); 12, 21, 22 = TM x TN tiles per wave: oss_conv1x1_wgrad_set_tile (tests, A-B timing)
+static std::atomic<int> g_wgrad_tile{0};
 void conv1x1_wgrad_set_tile(int mode) { g_wgrad_tile.store((mode == 12 || mode == 21 || mode == 22) ? mode : 0); }
 
 template <typename T>
@@ -1150,75 +1098,55 @@ int conv1x1_wgrad_slabs(int P) { return (P + kWgradSlab - 1) / kWgradSlab; }
 // Pixels per partial product of the GROUPED launch, in units of kWgradSlab.  One-problem launches keep 1 (they need every
 // workgroup they can get); in the grouped launch thousands of workgroups are queued anyway and every partial vector is
 // M x N floats written once and read once by the finishing sum -- at 512 pixels the headline step moved 0.9 GB of partials
-// each way (the finishing launch ran 222 us at memory speed).  Initial value from VMAMBAIR_WGRAD_SPAN.
-static std::atomic<int> g_wgrad_span{-1};
-static int wgrad_span_mult() {
-    int m = g_wgrad_span.load();
-    if (m < 0) {
-        const char *e = std::getenv("VMAMBAIR_WGRAD_SPAN");
-        m = e ? std::atoi(e) : 4;
-        m = m < 1 ? 1 : (m > 64 ? 64 : m);
-        g_wgrad_span.store(m);
-    }
-    return m;
-}
+// each way (the finishing launch ran 222 us at memory speed).  oss_conv1x1_wgrad_set_span changes it.
+static std::atomic<int> g_wgrad_span{4};
 void conv1x1_wgrad_set_span(int mult) { g_wgrad_span.store(mult < 1 ? 1 : (mult > 64 ? 64 : mult)); }
 
 int conv1x1_wgrad(oss_dtype io, const void *dy, const void *x, float *dw, float *part, int B, int M, int N, int P,
                   int64_t gsb, int64_t gsm, int64_t xsb, int64_t xsn, hipStream_t s, int G, int64_t gsg, int64_t xsg, int Mh,
                   int64_t gs_hi, float *db, int f32_split) {
-    const int NB = N + (db ? 1 : 0);
-    if (G < 1 || (size_t)B * G > 65535) return OSS_ERR_SHAPE;
-    if (io == OSS_F32) {   // plain 1x1 weight gradient only (the projection products call rows_f32_wgrad themselves)
-        if (G != 1 || (Mh > 0 && Mh != M)) return OSS_ERR_SHAPE;
-        return rows_f32_wgrad(reinterpret_cast<const float *>(dy), reinterpret_cast<const float *>(x), dw, part, B, 1, 1, M, N, P, gsb, 0,
-                              gsm, xsb, 0, xsn, s, db, f32_split);
-    }
-    if (Mh <= 0 || Mh > M) Mh = M;
-    int slabs = conv1x1_wgrad_slabs(P);
-    const int tiles = ((M + 31) / 32) * ((NB + 31) / 32);
-    dim3 grid(slabs, B * G, (tiles + 3) / 4);
-    const int tmode = wgrad_tile_mode();
-    if (defer_wgrad() && !tmode && (io == OSS_BF16 || io == OSS_F16) && (size_t)slabs * B * G * ((tiles + 3) / 4) < (1u << 24)) {
-        // a recorded product's partials do not exist until oss_flush_wgrads: its finishing sum must be deferred too (it would
-        // otherwise run right below, on a buffer nobody has written yet)
-        if (!defer_finish()) return OSS_ERR_WORKSPACE;
-        WgradDesc d;
-        d.span = kWgradSlab * wgrad_span_mult(); d.reserved_ = 0;
-        slabs = (P + d.span - 1) / d.span;   // never more than conv1x1_wgrad_slabs(P): the caller's partial buffer is large enough
-        d.dy = dy; d.x = x; d.part = part;
-        d.gsb = gsb; d.gsm = gsm; d.xsb = xsb; d.xsn = xsn; d.gsg = gsg; d.xsg = xsg; d.gs_hi = gs_hi;
-        d.M = M; d.N = N; d.P = P; d.G = G; d.Mh = Mh; d.NB = NB; d.slabs = slabs; d.bgs = B * G;
-        d.first_block = 0; d.io = (int)io;
-        defer_wgrad_push(&d, sizeof(d), (unsigned)(slabs * B * G * ((tiles + 3) / 4)));
-    } else
-    if (tmode && (io == OSS_BF16 || io == OSS_F16)) {
-        if (io == OSS_BF16)
-            wgrad_tiles_launch<bf16_t>(tmode, reinterpret_cast<const bf16_t *>(dy), reinterpret_cast<const bf16_t *>(x), part, B, M, N, P,
-                                       gsb, gsm, xsb, xsn, G, gsg, xsg, Mh, gs_hi, NB, slabs, s);
-        else
-            wgrad_tiles_launch<f16_t>(tmode, reinterpret_cast<const f16_t *>(dy), reinterpret_cast<const f16_t *>(x), part, B, M, N, P,
-                                      gsb, gsm, xsb, xsn, G, gsg, xsg, Mh, gs_hi, NB, slabs, s);
-    } else
-    switch (io) {
-        case OSS_BF16:
-            hipLaunchKernelGGL(oss_conv1x1_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(dy),
-                               reinterpret_cast<const bf16_t *>(x), part, M, N, P, gsb, gsm, xsb, xsn, G, gsg, xsg, Mh, gs_hi, NB);
-            break;
-        case OSS_F16:
-            hipLaunchKernelGGL(oss_conv1x1_wgrad_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(dy),
-                               reinterpret_cast<const f16_t *>(x), part, M, N, P, gsb, gsm, xsb, xsn, G, gsg, xsg, Mh, gs_hi, NB);
-            break;
-        default: return OSS_ERR_SHAPE;
-    }
-    if (db && G != 1) return OSS_ERR_SHAPE;
-    const size_t nw = (size_t)G * M * N, pvec = nw + (db ? M : 0);
-    if (defer_finish())
-        defer_sum(part, slabs * B, pvec, pvec, dw, nw, db);
-    else
-        hipLaunchKernelGGL(oss_conv1x1_wgrad_finish, dim3((unsigned)((pvec + 63) / 64)), dim3(256), 0, s, part, dw, db, slabs * B,
-                           pvec, nw);
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *gp = reinterpret_cast<const T *>(dy), *xp = reinterpret_cast<const T *>(x);
+        const int NB = N + (db ? 1 : 0);
+        if (G < 1 || (size_t)B * G > 65535) return OSS_ERR_SHAPE;
+        if constexpr (sizeof(T) == 4) {   // plain 1x1 weight gradient only (the projection products call rows_f32_wgrad themselves)
+            if (G != 1 || (Mh > 0 && Mh != M)) return OSS_ERR_SHAPE;
+            return rows_f32_wgrad(gp, xp, dw, part, B, 1, 1, M, N, P, gsb, 0, gsm, xsb, 0, xsn, s, db, f32_split);
+        } else {
+            if (Mh <= 0 || Mh > M) Mh = M;
+            int slabs = conv1x1_wgrad_slabs(P);
+            const int tiles = ((M + 31) / 32) * ((NB + 31) / 32);
+            dim3 grid(slabs, B * G, (tiles + 3) / 4);
+            const int tmode = g_wgrad_tile.load();
+            if (defer_wgrad() && !tmode && (size_t)slabs * B * G * ((tiles + 3) / 4) < (1u << 24)) {
+                // a recorded product's partials do not exist until oss_flush_wgrads: its finishing sum must be deferred too (it would
+                // otherwise run right below, on a buffer nobody has written yet)
+                if (!defer_finish()) return OSS_ERR_WORKSPACE;
+                WgradDesc d;
+                d.span = kWgradSlab * g_wgrad_span.load(); d.reserved_ = 0;
+                slabs = (P + d.span - 1) / d.span;   // never more than conv1x1_wgrad_slabs(P): the caller's partial buffer is large enough
+                d.dy = dy; d.x = x; d.part = part;
+                d.gsb = gsb; d.gsm = gsm; d.xsb = xsb; d.xsn = xsn; d.gsg = gsg; d.xsg = xsg; d.gs_hi = gs_hi;
+                d.M = M; d.N = N; d.P = P; d.G = G; d.Mh = Mh; d.NB = NB; d.slabs = slabs; d.bgs = B * G;
+                d.first_block = 0; d.io = (int)io;
+                defer_wgrad_push(&d, sizeof(d), (unsigned)(slabs * B * G * ((tiles + 3) / 4)));
+            } else if (tmode) {
+                wgrad_tiles_launch<T>(tmode, gp, xp, part, B, M, N, P, gsb, gsm, xsb, xsn, G, gsg, xsg, Mh, gs_hi, NB, slabs, s);
+            } else {
+                hipLaunchKernelGGL(oss_conv1x1_wgrad_kernel<T>, grid, dim3(256), 0, s, gp, xp, part, M, N, P, gsb, gsm, xsb, xsn, G, gsg,
+                                   xsg, Mh, gs_hi, NB);
+            }
+            if (db && G != 1) return OSS_ERR_SHAPE;
+            const size_t nw = (size_t)G * M * N, pvec = nw + (db ? M : 0);
+            if (defer_finish())
+                defer_sum(part, slabs * B, pvec, pvec, dw, nw, db);
+            else
+                hipLaunchKernelGGL(oss_conv1x1_wgrad_finish, dim3((unsigned)((pvec + 63) / 64)), dim3(256), 0, s, part, dw, db, slabs * B,
+                                   pvec, nw);
+            return (int)hipGetLastError();
+        }
+    });
 }
 
 // ---- grouped weight gradients: flush (oss_capi.hip keeps the recorded descriptors as raw bytes + block counts) -----------------
@@ -1226,15 +1154,11 @@ size_t wgrad_desc_bytes() { return sizeof(WgradDesc); }
 // descs: n descriptors in host memory with first_block filled; d_descs / d_map: their device copies (already queued on s)
 int wgrad_grouped_launch(int io, const void *d_descs, const void *d_map, unsigned total_blocks, hipStream_t s) {
     if (total_blocks == 0) return 0;
-    if (io == OSS_BF16)
-        hipLaunchKernelGGL(oss_conv1x1_wgrad_grouped_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, s,
+    return io_dispatch<IO_16>((oss_dtype)io, [&](auto tag) {
+        hipLaunchKernelGGL(oss_conv1x1_wgrad_grouped_kernel<typename decltype(tag)::type>, dim3(total_blocks), dim3(256), 0, s,
                            reinterpret_cast<const WgradDesc *>(d_descs), reinterpret_cast<const uint16_t *>(d_map));
-    else if (io == OSS_F16)
-        hipLaunchKernelGGL(oss_conv1x1_wgrad_grouped_kernel<f16_t>, dim3(total_blocks), dim3(256), 0, s,
-                           reinterpret_cast<const WgradDesc *>(d_descs), reinterpret_cast<const uint16_t *>(d_map));
-    else
-        return OSS_ERR_SHAPE;
-    return (int)hipGetLastError();
+        return (int)hipGetLastError();
+    });
 }
 void wgrad_desc_set_first_block(void *desc, unsigned first) { reinterpret_cast<WgradDesc *>(desc)->first_block = first; }
 int wgrad_desc_io(const void *desc) { return reinterpret_cast<const WgradDesc *>(desc)->io; }

@@ -15,7 +15,6 @@
 //   4. sends the results through a wave-private LDS tile and out as 16-byte stores along the pixel axis.
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <type_traits>
 #include "oss_device.h"
 #include "oss_host.h"
@@ -309,22 +308,15 @@ static size_t wg_lds_bytes(int K, int pt, bool res) { return (size_t)K * 2 * (pt
 // (tools/conv_wg_test.py, and inside the SR and Deraining steps): K = 96 / 192 want 128 pixels when that still gives a
 // workgroup per CU, K <= 48 wants 64; a launch with fewer workgroups than CUs (Deraining levels 1.. at batch 4) loses to the
 // wave-level kernels unless its row tiles are split over more workgroups.
-static std::atomic<int> g_wg_pixels{-1};
+static std::atomic<int> g_wg_pixels{0};
 void conv1x1_wg_set_pixels(int pt) { g_wg_pixels.store(pt == 64 || pt == 128 ? pt : 0); }
 static void wg_shape(int B, int M, int K, int P, int &pt, int &nz) {
-    int f = g_wg_pixels.load();
-    if (f < 0) {
-        const char *e = std::getenv("VMAMBAIR_CONV1X1_WG_PIXELS");
-        const int v = e ? std::atoi(e) : 0;
-        f = (v == 64 || v == 128) ? v : 0;
-        g_wg_pixels.store(f);
-    }
+    const int f = g_wg_pixels.load();
     const long t128 = (long)B * (P / 128);
     pt = f ? f : ((K <= 48 && t128 < 1024) || t128 < 256 ? 64 : 128);
     const long wgs = (long)B * (P / pt);
     const int groups = ((M + 31) / 32 + 3) / 4;           // row tiles in units of a workgroup's four waves
-    static const int target = [] { const char *e = std::getenv("VMAMBAIR_CONV1X1_WG_TARGET"); return e ? std::atoi(e) : 256; }();
-    nz = (int)std::min<long>(groups, (target + wgs - 1) / wgs);
+    nz = (int)std::min<long>(groups, (256 + wgs - 1) / wgs);   // a workgroup per CU
     if (nz < 1) nz = 1;
 }
 
@@ -336,7 +328,7 @@ int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, c
     // wave-level kernel (10.6 vs 9.4 us at 96 -> 96: the residual arrives cold from HBM behind the fp32 LDS round trip), so
     // those calls stay where they were and the RES instantiations are not built.
     if (res) return 0;
-    if (io != OSS_BF16 && io != OSS_F16) return 0;
+    if (!io_ok<IO_16>(io)) return 0;
     if (K % 16 != 0 || K < 16 || K > 192 || P % 128 != 0 || M < 1) return 0;
     // built for the widths a power-of-two-times-{1,3} base width gives (K = 16, 32, 48, 64, 96, 128, 192: dim 16 / 32 / 48 / 64 and
     // their doublings); K = 80, 112, 144, 160, 176 stay on the wave-level kernels (round 5: 80 instantiations nobody launched)
@@ -384,15 +376,13 @@ static int wg_launch(const T *x, const float *w, const float *bias, T *y, int B,
 int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
                int64_t xsk, int wt, hipStream_t s, const void *res) {
     if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res)) return OSS_ERR_SHAPE;
-    if (io == OSS_BF16)
-        return wt ? wg_launch<bf16_t, true>(reinterpret_cast<const bf16_t *>(x), w, bias, reinterpret_cast<bf16_t *>(y), B, M, K, P, xsb, xsk,
-                                            reinterpret_cast<const bf16_t *>(res), s)
-                  : wg_launch<bf16_t, false>(reinterpret_cast<const bf16_t *>(x), w, bias, reinterpret_cast<bf16_t *>(y), B, M, K, P, xsb, xsk,
-                                             reinterpret_cast<const bf16_t *>(res), s);
-    return wt ? wg_launch<f16_t, true>(reinterpret_cast<const f16_t *>(x), w, bias, reinterpret_cast<f16_t *>(y), B, M, K, P, xsb, xsk,
-                                       reinterpret_cast<const f16_t *>(res), s)
-              : wg_launch<f16_t, false>(reinterpret_cast<const f16_t *>(x), w, bias, reinterpret_cast<f16_t *>(y), B, M, K, P, xsb, xsk,
-                                        reinterpret_cast<const f16_t *>(res), s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *xp = reinterpret_cast<const T *>(x), *rp = reinterpret_cast<const T *>(res);
+        T *yp = reinterpret_cast<T *>(y);
+        return wt ? wg_launch<T, true>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s)
+                  : wg_launch<T, false>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s);
+    });
 }
 
 // ---- input gradient of a 1x1 convolution + the backward of the LayerNorm in front of it, one launch ---------------------------
@@ -598,7 +588,7 @@ oss_wg_lnbwd_finish(const float *__restrict__ part, float *__restrict__ dw, floa
 size_t conv1x1_dgrad_lnbwd_partial_floats(int B, int M, int P) { return (size_t)B * (P / 64) * 2 * M; }
 
 int conv1x1_dgrad_lnbwd_ok(oss_dtype io, int M, int K, int P, int B) {
-    if (io != OSS_BF16 && io != OSS_F16) return 0;
+    if (!io_ok<IO_16>(io)) return 0;
     if (K % 16 != 0 || K < 2 * M || K > 192 || M < 1 || M > 128 || P % 128 != 0) return 0;
     const int ks = K / 16;
     // (An any-K form for project_in after norm2 -- K = 2 hidden = 510, 64-pixel workgroups, weights fetched in chunks of 8 k-steps --
@@ -647,28 +637,23 @@ int conv1x1_dgrad_lnbwd(oss_dtype io, const void *dy, const float *w, const void
     if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(dx) |
          reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(rstd)) & 15u)
         return OSS_ERR_SHAPE;
-    if (io == OSS_BF16) {
-        WgLnBwdArgs<bf16_t> a{reinterpret_cast<const bf16_t *>(x), ln_w, mean, rstd, reinterpret_cast<const bf16_t *>(skip),
-                              reinterpret_cast<bf16_t *>(dx), part, with_bias};
-        return lnbwd_launch<bf16_t>(reinterpret_cast<const bf16_t *>(dy), w, B, M, K, P, xsb, xsk, a, dlw, dlb, s);
-    }
-    WgLnBwdArgs<f16_t> a{reinterpret_cast<const f16_t *>(x), ln_w, mean, rstd, reinterpret_cast<const f16_t *>(skip),
-                         reinterpret_cast<f16_t *>(dx), part, with_bias};
-    return lnbwd_launch<f16_t>(reinterpret_cast<const f16_t *>(dy), w, B, M, K, P, xsb, xsk, a, dlw, dlb, s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        WgLnBwdArgs<T> a{reinterpret_cast<const T *>(x), ln_w, mean, rstd, reinterpret_cast<const T *>(skip), reinterpret_cast<T *>(dx), part,
+                         with_bias};
+        return lnbwd_launch<T>(reinterpret_cast<const T *>(dy), w, B, M, K, P, xsb, xsk, a, dlw, dlb, s);
+    });
 }
 
 // n = LayerNorm(x) (ln_w, ln_b or NULL), mean, rstd written out; y = W n + bias.  Same shape rules as conv1x1_wg (forward only).
 int ln_conv1x1_wg(oss_dtype io, const void *x, const float *ln_w, const float *ln_b, float eps, void *n, float *mean, float *rstd,
                   const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s) {
     if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, nullptr) || (reinterpret_cast<uintptr_t>(n) & 15u)) return OSS_ERR_SHAPE;
-    if (io == OSS_BF16) {
-        WgLnArgs<bf16_t> a{ln_w, ln_b, reinterpret_cast<bf16_t *>(n), mean, rstd, eps};
-        return wg_launch<bf16_t, false, true>(reinterpret_cast<const bf16_t *>(x), w, bias, reinterpret_cast<bf16_t *>(y), B, M, K, P, xsb,
-                                              xsk, nullptr, s, a);
-    }
-    WgLnArgs<f16_t> a{ln_w, ln_b, reinterpret_cast<f16_t *>(n), mean, rstd, eps};
-    return wg_launch<f16_t, false, true>(reinterpret_cast<const f16_t *>(x), w, bias, reinterpret_cast<f16_t *>(y), B, M, K, P, xsb, xsk,
-                                         nullptr, s, a);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        WgLnArgs<T> a{ln_w, ln_b, reinterpret_cast<T *>(n), mean, rstd, eps};
+        return wg_launch<T, false, true>(reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), B, M, K, P, xsb, xsk, nullptr, s, a);
+    });
 }
 
 }  // namespace oss

@@ -386,7 +386,7 @@ static bool dense_vec(int W, std::initializer_list<const void *> ptrs, std::init
 }
 
 int conv3x3_dense_ok(oss_dtype io, int Cin, int Cout, int H, int W) {
-    if (io != OSS_F16 && io != OSS_BF16) return 0;
+    if (!io_ok<IO_16>(io)) return 0;
     if (Cin < 16 || Cin % 16 != 0 || Cin > 16384 || Cout < 5 || Cout > 16384) return 0;
     if (H < 1 || W < 1 || H > 32768 || W > 32768) return 0;   // every grid axis and every in-plane index stays far inside its limits
     return 1;
@@ -423,16 +423,18 @@ static int dense_launch(const void *x, const float *w, const float *bias, void *
 int conv3x3_dense_fwd(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int Cin, int Cout, int H, int W,
                       int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, hipStream_t s) {
     if (!conv3x3_dense_ok(io, Cin, Cout, H, W) || B <= 0 || B > 65535) return OSS_ERR_SHAPE;
-    return io == OSS_F16 ? dense_launch<f16_t, false>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, s)
-                         : dense_launch<bf16_t, false>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        return dense_launch<typename decltype(tag)::type, false>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, s);
+    });
 }
 
 // dx[ci] = sum_co sum_t W[co][ci][8 - t] dy[co][p + off(t)]: the forward body with the roles of Cin and Cout swapped
 int conv3x3_dense_dgrad(oss_dtype io, const void *dy, const float *w, void *dx, int B, int Cin, int Cout, int H, int W, int64_t gsb,
                         int64_t gsc, int64_t dsb, int64_t dsc, hipStream_t s) {
     if (!conv3x3_dense_ok(io, Cin, Cout, H, W) || B <= 0 || B > 65535) return OSS_ERR_SHAPE;
-    return io == OSS_F16 ? dense_launch<f16_t, true>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, s)
-                         : dense_launch<bf16_t, true>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        return dense_launch<typename decltype(tag)::type, true>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, s);
+    });
 }
 
 // rows per band: about 512 workgroups in all (two per CU), never more bands than rows
@@ -467,10 +469,12 @@ int conv3x3_dense_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, 
         hipLaunchKernelGGL((oss_conv3x3_dense_dbias_kernel<TT, V_>), dim3(Cout), dim3(1024), 0, s, reinterpret_cast<const TT *>(dy), db, \
                            B, H, W, gsb, gsc);                                                                                      \
     } while (0)
-    if (io == OSS_F16) { using TT = f16_t; if (vec) OSS_DENSE_WG(true); else OSS_DENSE_WG(false); }
-    else { using TT = bf16_t; if (vec) OSS_DENSE_WG(true); else OSS_DENSE_WG(false); }
+    const int rc = io_dispatch<IO_16>(io, [&](auto tag) {
+        using TT = typename decltype(tag)::type;
+        if (vec) OSS_DENSE_WG(true); else OSS_DENSE_WG(false);
+        return (int)hipGetLastError();
+    });
 #undef OSS_DENSE_WG
-    const int rc = (int)hipGetLastError();
     if (rc != 0) return rc;
     if (defer_finish())
         defer_sum(part, B * bands, pvec, nw, dw, nw, nullptr);

@@ -223,7 +223,7 @@ static bool thin_aligned(std::initializer_list<const void *> ptrs, std::initiali
 }
 
 int conv3x3_thin_ok(oss_dtype io, int Cin, int Cout, int H, int W) {
-    if (io != OSS_F16 && io != OSS_BF16) return 0;
+    if (!io_ok<IO_16>(io)) return 0;
     if (Cin < 1 || Cout < 1 || H < 1 || W < 8 || W % 8 != 0 || W > 4096) return 0;
     return (Cin <= 4 || Cout <= 4) ? 1 : 0;
 }
@@ -274,32 +274,34 @@ static int thin_expand(const void *x, const float *w, const float *bias, void *y
 
 int conv3x3_thin_fwd(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int Cin, int Cout, int H, int W,
                      int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, hipStream_t s) {
-    if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({x, y}, {xsb, xsc, ysb, ysc})) return OSS_ERR_SHAPE;
-    if (B <= 0 || B > 65535) return OSS_ERR_SHAPE;
-    // weight (Cout, Cin, 3, 3): element (co, ci, t) at co * Cin * 9 + ci * 9 + t
-    if (Cout <= 4) {   // reduce: thin index f = co, wide index c = ci
-        const ThinW ws{(int64_t)Cin * 9, 9, 0};
-        return io == OSS_F16 ? thin_reduce<f16_t>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, ws, s)
-                             : thin_reduce<bf16_t>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, ws, s);
-    }
-    const ThinW ws{9, (int64_t)Cin * 9, 0};   // expand: f = ci, c = co
-    return io == OSS_F16 ? thin_expand<f16_t>(x, w, bias, y, B, Cout, Cin, H, W, xsb, xsc, ysb, ysc, ws, s)
-                         : thin_expand<bf16_t>(x, w, bias, y, B, Cout, Cin, H, W, xsb, xsc, ysb, ysc, ws, s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({x, y}, {xsb, xsc, ysb, ysc})) return OSS_ERR_SHAPE;
+        if (B <= 0 || B > 65535) return OSS_ERR_SHAPE;
+        // weight (Cout, Cin, 3, 3): element (co, ci, t) at co * Cin * 9 + ci * 9 + t
+        if (Cout <= 4) {   // reduce: thin index f = co, wide index c = ci
+            const ThinW ws{(int64_t)Cin * 9, 9, 0};
+            return thin_reduce<T>(x, w, bias, y, B, Cin, Cout, H, W, xsb, xsc, ysb, ysc, ws, s);
+        }
+        const ThinW ws{9, (int64_t)Cin * 9, 0};   // expand: f = ci, c = co
+        return thin_expand<T>(x, w, bias, y, B, Cout, Cin, H, W, xsb, xsc, ysb, ysc, ws, s);
+    });
 }
 
 // dx[ci] = sum_co sum_t W[co][ci][8 - t] dy[co][p + t]   (the transposed convolution: taps mirrored, weight read transposed)
 int conv3x3_thin_dgrad(oss_dtype io, const void *dy, const float *w, void *dx, int B, int Cin, int Cout, int H, int W, int64_t gsb,
                        int64_t gsc, int64_t dsb, int64_t dsc, hipStream_t s) {
-    if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({dy, dx}, {gsb, gsc, dsb, dsc})) return OSS_ERR_SHAPE;
-    if (B <= 0 || B > 65535) return OSS_ERR_SHAPE;
-    if (Cout <= 4) {   // expand dy (F = Cout planes) to the Cin planes of dx: f = co, c = ci
-        const ThinW ws{(int64_t)Cin * 9, 9, 1};
-        return io == OSS_F16 ? thin_expand<f16_t>(dy, w, nullptr, dx, B, Cin, Cout, H, W, gsb, gsc, dsb, dsc, ws, s)
-                             : thin_expand<bf16_t>(dy, w, nullptr, dx, B, Cin, Cout, H, W, gsb, gsc, dsb, dsc, ws, s);
-    }
-    const ThinW ws{9, (int64_t)Cin * 9, 1};   // reduce the Cout planes of dy to the F = Cin planes of dx: f = ci, c = co
-    return io == OSS_F16 ? thin_reduce<f16_t>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, ws, s)
-                         : thin_reduce<bf16_t>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, ws, s);
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({dy, dx}, {gsb, gsc, dsb, dsc})) return OSS_ERR_SHAPE;
+        if (B <= 0 || B > 65535) return OSS_ERR_SHAPE;
+        if (Cout <= 4) {   // expand dy (F = Cout planes) to the Cin planes of dx: f = co, c = ci
+            const ThinW ws{(int64_t)Cin * 9, 9, 1};
+            return thin_expand<T>(dy, w, nullptr, dx, B, Cin, Cout, H, W, gsb, gsc, dsb, dsc, ws, s);
+        }
+        const ThinW ws{9, (int64_t)Cin * 9, 1};   // reduce the Cout planes of dy to the F = Cin planes of dx: f = ci, c = co
+        return thin_reduce<T>(dy, w, nullptr, dx, B, Cout, Cin, H, W, gsb, gsc, dsb, dsc, ws, s);
+    });
 }
 
 size_t conv3x3_thin_wgrad_partial_floats(int B, int Cin, int Cout) { return (size_t)B * ((size_t)Cin * Cout * 9 + Cout); }
@@ -323,30 +325,31 @@ static int thin_wgrad(const void *few, const void *many, float *part, int B, int
 // dw[co][ci][t] = sum_{b,p} dy[co][p] x[ci][p + t],  db[co] = sum dy[co]
 int conv3x3_thin_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, float *db, float *part, int B, int Cin, int Cout, int H,
                        int W, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, hipStream_t s) {
-    if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({x, dy}, {xsb, xsc, gsb, gsc})) return OSS_ERR_SHAPE;
-    if (B <= 0 || B > 65535 || !dw || !part) return OSS_ERR_NULL;
-    const size_t nw = (size_t)Cin * Cout * 9, pvec = nw + Cout;
-    int rc;
-    if (Cout <= 4) {
-        // few = dy (f = co), many = x (c = ci): S[c][f][t] is dw[f][c][t]
-        const ThinP pp{(int64_t)pvec, (int64_t)Cin * 9, 9, (int64_t)nw, 0};
-        rc = io == OSS_F16 ? thin_wgrad<f16_t>(dy, x, part, B, Cin, Cout, H, W, gsb, gsc, xsb, xsc, pp, db != nullptr, s)
-                           : thin_wgrad<bf16_t>(dy, x, part, B, Cin, Cout, H, W, gsb, gsc, xsb, xsc, pp, db != nullptr, s);
-    } else {
-        // few = x (f = ci), many = dy (c = co): sum_p x[f][p] dy[c][p + t] = sum_q dy[c][q] x[f][q - t] = dw[c][f][8 - t];
-        // the bias gradient sums the MANY side here, which this kernel does not do: the caller's reduction (db == NULL only)
-        if (db) return OSS_ERR_SHAPE;
-        const ThinP pp{(int64_t)pvec, 9, (int64_t)Cin * 9, (int64_t)nw, 1};
-        rc = io == OSS_F16 ? thin_wgrad<f16_t>(x, dy, part, B, Cout, Cin, H, W, xsb, xsc, gsb, gsc, pp, false, s)
-                           : thin_wgrad<bf16_t>(x, dy, part, B, Cout, Cin, H, W, xsb, xsc, gsb, gsc, pp, false, s);
-    }
-    if (rc != 0) return rc;
-    const size_t nout = nw + (db ? Cout : 0);
-    if (defer_finish())
-        defer_sum(part, B, pvec, nout, dw, nw, db);
-    else
-        hipLaunchKernelGGL(oss_conv3x3_thin_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, part, dw, db, B, pvec, nw, nout);
-    return (int)hipGetLastError();
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (!conv3x3_thin_ok(io, Cin, Cout, H, W) || !thin_aligned({x, dy}, {xsb, xsc, gsb, gsc})) return OSS_ERR_SHAPE;
+        if (B <= 0 || B > 65535 || !dw || !part) return OSS_ERR_NULL;
+        const size_t nw = (size_t)Cin * Cout * 9, pvec = nw + Cout;
+        int rc;
+        if (Cout <= 4) {
+            // few = dy (f = co), many = x (c = ci): S[c][f][t] is dw[f][c][t]
+            const ThinP pp{(int64_t)pvec, (int64_t)Cin * 9, 9, (int64_t)nw, 0};
+            rc = thin_wgrad<T>(dy, x, part, B, Cin, Cout, H, W, gsb, gsc, xsb, xsc, pp, db != nullptr, s);
+        } else {
+            // few = x (f = ci), many = dy (c = co): sum_p x[f][p] dy[c][p + t] = sum_q dy[c][q] x[f][q - t] = dw[c][f][8 - t];
+            // the bias gradient sums the MANY side here, which this kernel does not do: the caller's reduction (db == NULL only)
+            if (db) return OSS_ERR_SHAPE;
+            const ThinP pp{(int64_t)pvec, 9, (int64_t)Cin * 9, (int64_t)nw, 1};
+            rc = thin_wgrad<T>(x, dy, part, B, Cout, Cin, H, W, xsb, xsc, gsb, gsc, pp, false, s);
+        }
+        if (rc != 0) return rc;
+        const size_t nout = nw + (db ? Cout : 0);
+        if (defer_finish())
+            defer_sum(part, B, pvec, nout, dw, nw, db);
+        else
+            hipLaunchKernelGGL(oss_conv3x3_thin_finish, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, part, dw, db, B, pvec, nw, nout);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace oss

@@ -674,13 +674,9 @@ static int dwconv_launch(const void *x, const float *w, const float *bias, void 
 
 int dwconv3x3(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int C, int H, int W,
               int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, int flip, hipStream_t s, void *pre, int act) {
-    switch (io) {
-        case OSS_F32: return dwconv_launch<float>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
-        case OSS_F16: return dwconv_launch<f16_t>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
-        case OSS_BF16: return dwconv_launch<bf16_t>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
-        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
-    }
-    return OSS_ERR_SHAPE;
+    return io_dispatch(io, [&](auto tag) {
+        return dwconv_launch<typename decltype(tag)::type>(x, w, bias, y, B, C, H, W, xsb, xsc, ysb, ysc, flip, s, pre, act);
+    });
 }
 
 // ---- fused forms: host side ------------------------------------------------------------------------------------------
@@ -690,9 +686,9 @@ static size_t fused_lds_bytes(int nch, int H, int W, size_t esize) { return (siz
 // channel (pair)'s planes in LDS
 static bool dw_edge(int W) { return (64 % (W / 8)) != 0; }
 int dwconv3x3_fused_ok(oss_dtype io, int H, int W, int nch) {
-    if (io != OSS_F16 && io != OSS_BF16 && io != OSS_F32) return 0;   // (float I/O: round 4 -- the reference's own training precision)
+    if (!io_ok(io)) return 0;   // (float I/O: round 4 -- the reference's own training precision)
     if (nch < 1 || nch > 2 || H <= 0 || W <= 0 || W % 8 != 0 || W > 512) return 0;
-    return fused_lds_bytes(nch, H, W, io == OSS_F32 ? 4 : 2) + 4 * 20 * sizeof(float) <= kMaxLdsBytes ? 1 : 0;
+    return fused_lds_bytes(nch, H, W, io_bytes(io)) + 4 * 20 * sizeof(float) <= kMaxLdsBytes ? 1 : 0;
 }
 
 static bool aligned16(std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> strides) {
@@ -720,16 +716,16 @@ static int dwgate_fwd_launch(const void *t, const float *w, const float *bias, v
 // the forward alone streams (three rows per lane group, nothing in LDS): any plane of rows of W / 8 <= 64 lane groups -- the inference
 // path of planes too large for the backward's LDS-resident form (RealSR at 272 x 272 tiles and untiled 512 x 512)
 int dwgate_fwd_ok(oss_dtype io, int H, int W) {
-    if (io != OSS_F16 && io != OSS_BF16 && io != OSS_F32) return 0;
+    if (!io_ok(io)) return 0;
     return (H > 0 && W > 0 && W % 8 == 0 && W <= 512) ? 1 : 0;
 }
 
 int dwgate_fwd(oss_dtype io, const void *t, const float *w, const float *bias, void *out, int B, int Hd, int H, int W,
                int64_t tsb, int64_t tsc, int64_t osb, int64_t osc, hipStream_t s) {
     if (!dwgate_fwd_ok(io, H, W)) return OSS_ERR_SHAPE;
-    if (io == OSS_F32) return dwgate_fwd_launch<float>(t, w, bias, out, B, Hd, H, W, tsb, tsc, osb, osc, s);
-    return io == OSS_F16 ? dwgate_fwd_launch<f16_t>(t, w, bias, out, B, Hd, H, W, tsb, tsc, osb, osc, s)
-                         : dwgate_fwd_launch<bf16_t>(t, w, bias, out, B, Hd, H, W, tsb, tsc, osb, osc, s);
+    return io_dispatch(io, [&](auto tag) {
+        return dwgate_fwd_launch<typename decltype(tag)::type>(t, w, bias, out, B, Hd, H, W, tsb, tsc, osb, osc, s);
+    });
 }
 
 template <typename T, int MODE>
@@ -741,14 +737,13 @@ static int bwd_fused_launch(const void *x, const float *w, const float *bias, co
     static LdsGate gate, gate_e, gate_k;
     const size_t smem = fused_lds_bytes(NCH, H, W, sizeof(T));
     const bool edge = dw_edge(W);
-    static const bool keep_ok = [] { const char *e = getenv("VMAMBAIR_DW_KEEP"); return !(e && e[0] == '0'); }();   // A-B timing
     // <= 2 groups per lane: the centre rows of x stay in registers (16-bit I/O: the float form's raw rows are twice the registers and
     // end up in scratch memory -- it keeps the row-by-row loads)
     bool keep = false;
     auto kern = edge ? oss_dwconv3x3_bwd_fused_kernel<T, MODE, true, false> : oss_dwconv3x3_bwd_fused_kernel<T, MODE, false, false>;
     LdsGate *g = edge ? &gate_e : &gate;
     if constexpr (sizeof(T) == 2) {
-        keep = keep_ok && !edge && (W / 8) * H <= 512;
+        keep = !edge && (W / 8) * H <= 512;
         if (keep) { kern = oss_dwconv3x3_bwd_fused_kernel<T, MODE, false, true>; g = &gate_k; }
         if constexpr (MODE == kDwSilu) {
             static LdsGate gate_m;
@@ -790,9 +785,9 @@ static int flat2_fwd_launch(const void *x, const float *w, const float *bias, vo
 int dwconv3x3_silu_flat2_fwd(oss_dtype io, const void *x, const float *w, const float *bias, void *x2, int B, int C, int H, int W,
                              int64_t xsb, int64_t xsc, hipStream_t s) {
     if (!dwconv3x3_flat2_ok(io, H, W)) return OSS_ERR_SHAPE;
-    if (io == OSS_F32) return flat2_fwd_launch<float>(x, w, bias, x2, B, C, H, W, xsb, xsc, s);
-    return io == OSS_F16 ? flat2_fwd_launch<f16_t>(x, w, bias, x2, B, C, H, W, xsb, xsc, s)
-                         : flat2_fwd_launch<bf16_t>(x, w, bias, x2, B, C, H, W, xsb, xsc, s);
+    return io_dispatch(io, [&](auto tag) {
+        return flat2_fwd_launch<typename decltype(tag)::type>(x, w, bias, x2, B, C, H, W, xsb, xsc, s);
+    });
 }
 
 int dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *w, const float *bias, const void *g2, void *dx, float *dw,
@@ -800,10 +795,11 @@ int dwconv3x3_silu_flat2_bwd(oss_dtype io, const void *x, const float *w, const 
                              hipStream_t s) {
     if (!dwconv3x3_flat2_ok(io, H, W)) return OSS_ERR_SHAPE;
     const int64_t L = (int64_t)H * W;
-    const char *gt = reinterpret_cast<const char *>(g2) + (size_t)C * L * (io == OSS_F32 ? 4 : 2);
-    if (io == OSS_F32) return bwd_fused_launch<float, kDwSilu>(x, w, bias, g2, dx, dw, db, part, B, C, H, W, xsb, xsc, 2 * C * L, L, dsb, dsc, s, gt);
-    return io == OSS_F16 ? bwd_fused_launch<f16_t, kDwSilu>(x, w, bias, g2, dx, dw, db, part, B, C, H, W, xsb, xsc, 2 * C * L, L, dsb, dsc, s, gt)
-                         : bwd_fused_launch<bf16_t, kDwSilu>(x, w, bias, g2, dx, dw, db, part, B, C, H, W, xsb, xsc, 2 * C * L, L, dsb, dsc, s, gt);
+    const char *gt = reinterpret_cast<const char *>(g2) + (size_t)C * L * io_bytes(io);
+    return io_dispatch(io, [&](auto tag) {
+        return bwd_fused_launch<typename decltype(tag)::type, kDwSilu>(x, w, bias, g2, dx, dw, db, part, B, C, H, W, xsb, xsc, 2 * C * L, L,
+                                                                       dsb, dsc, s, gt);
+    });
 }
 
 int dwconv3x3_bwd_fused(oss_dtype io, int mode, const void *x, const float *w, const float *bias, const void *dy, void *dx,
@@ -811,14 +807,11 @@ int dwconv3x3_bwd_fused(oss_dtype io, int mode, const void *x, const float *w, c
                         int64_t gsc, int64_t dsb, int64_t dsc, hipStream_t s) {
     const int nch = mode == kDwGate ? 2 : 1;
     if (!dwconv3x3_fused_ok(io, H, W, nch) || C % nch != 0) return OSS_ERR_SHAPE;
-    if (io == OSS_F32)
-        return mode == kDwGate ? bwd_fused_launch<float, kDwGate>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s)
-                               : bwd_fused_launch<float, kDwSilu>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s);
-    if (mode == kDwGate)
-        return io == OSS_F16 ? bwd_fused_launch<f16_t, kDwGate>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s)
-                             : bwd_fused_launch<bf16_t, kDwGate>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s);
-    return io == OSS_F16 ? bwd_fused_launch<f16_t, kDwSilu>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s)
-                         : bwd_fused_launch<bf16_t, kDwSilu>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s);
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return mode == kDwGate ? bwd_fused_launch<T, kDwGate>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s)
+                               : bwd_fused_launch<T, kDwSilu>(x, w, bias, dy, dx, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, dsb, dsc, s);
+    });
 }
 
 template <typename T>
@@ -857,14 +850,10 @@ static int wgrad_launch(const void *x, const void *dy, float *dw, float *db, flo
 
 int dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, float *db, float *part, int B, int C, int H,
                     int W, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, hipStream_t s, const void *pre, void *dpre) {
-    if ((pre != nullptr) != (dpre != nullptr)) return OSS_ERR_NULL;
-    switch (io) {
-        case OSS_F32: return wgrad_launch<float>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
-        case OSS_F16: return wgrad_launch<f16_t>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
-        case OSS_BF16: return wgrad_launch<bf16_t>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
-        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
-    }
-    return OSS_ERR_SHAPE;
+    return io_dispatch(io, [&](auto tag) {
+        if ((pre != nullptr) != (dpre != nullptr)) return OSS_ERR_NULL;
+        return wgrad_launch<typename decltype(tag)::type>(x, dy, dw, db, part, B, C, H, W, xsb, xsc, gsb, gsc, s, pre, dpre);
+    });
 }
 
 }  // namespace oss

@@ -426,24 +426,21 @@ oss_effn_round_weights_kernel(const float *__restrict__ pin /*(2 h, D)*/, const 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 int effn_round_weights(oss_dtype io, const float *pin, const float *pdw, const float *pout, void *w_in, float *w_dw, void *w_out, int D,
                        int hidden, hipStream_t s) {
-    if (io != OSS_F16 && io != OSS_BF16) return OSS_ERR_SHAPE;
-    if (D < 1 || hidden < 1 || hidden > 16384 || D > 4096) return OSS_ERR_SHAPE;
-    const int HP = (hidden + 15) / 16 * 16;
-    const long total = 2L * HP * D + 2L * HP * 9 + (long)D * HP;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (io == OSS_F16)
-        hipLaunchKernelGGL(oss_effn_round_weights_kernel<f16_t>, grid, dim3(256), 0, s, pin, pdw, pout, reinterpret_cast<f16_t *>(w_in), w_dw,
-                           reinterpret_cast<f16_t *>(w_out), D, hidden, HP);
-    else
-        hipLaunchKernelGGL(oss_effn_round_weights_kernel<bf16_t>, grid, dim3(256), 0, s, pin, pdw, pout, reinterpret_cast<bf16_t *>(w_in), w_dw,
-                           reinterpret_cast<bf16_t *>(w_out), D, hidden, HP);
-    return (int)hipGetLastError();
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (D < 1 || hidden < 1 || hidden > 16384 || D > 4096) return OSS_ERR_SHAPE;
+        const int HP = (hidden + 15) / 16 * 16;
+        const long total = 2L * HP * D + 2L * HP * 9 + (long)D * HP;
+        hipLaunchKernelGGL(oss_effn_round_weights_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pin, pdw, pout,
+                           reinterpret_cast<T *>(w_in), w_dw, reinterpret_cast<T *>(w_out), D, hidden, HP);
+        return (int)hipGetLastError();
+    });
 }
 
 static constexpr bool effn_ks_built(int ks) { return ks == 2 || ks == 3 || ks == 4 || ks == 6; }
 
 int effn_fwd_ok(oss_dtype io, int D, int hidden, int H, int W) {
-    if (io != OSS_F16 && io != OSS_BF16) return 0;
+    if (!io_ok<IO_16>(io)) return 0;
     if (D % 16 != 0 || !effn_ks_built(D / 16) || hidden < 1 || hidden > 16384) return 0;
     return (H > 0 && W > 0 && W % 8 == 0) ? 1 : 0;
 }
@@ -473,16 +470,16 @@ int effn_fwd(oss_dtype io, const void *x, const float *ln_w, const float *ln_b, 
         if (st % 8 != 0) return OSS_ERR_SHAPE;
     if ((long)((W + 15) / 16) * ((H + 7) / 8) > 2147483647L) return OSS_ERR_SHAPE;
     EffnArgs a{x, out, ln_w, ln_b, w_in, w_dw, w_out, hidden, (hidden + 15) / 16 * 16, H, W, xsb, xsc, osb, osc, eps, 0};
-#define OSS_EFFN(KS_)                                                                         \
-    return io == OSS_F16 ? effn_launch<f16_t, KS_>(a, B, s) : effn_launch<bf16_t, KS_>(a, B, s)
-    switch (D / 16) {
-        case 2: OSS_EFFN(2);
-        case 3: OSS_EFFN(3);
-        case 4: OSS_EFFN(4);
-        case 6: OSS_EFFN(6);
-        default: return OSS_ERR_SHAPE;
-    }
-#undef OSS_EFFN
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        switch (D / 16) {
+            case 2: return effn_launch<T, 2>(a, B, s);
+            case 3: return effn_launch<T, 3>(a, B, s);
+            case 4: return effn_launch<T, 4>(a, B, s);
+            case 6: return effn_launch<T, 6>(a, B, s);
+            default: return OSS_ERR_SHAPE;
+        }
+    });
 }
 
 }  // namespace oss

@@ -61,27 +61,23 @@ oss_gelu_gate_bwd_kernel(const T *__restrict__ h, const T *__restrict__ dout, T 
 }
 
 int gelu_gate_fwd(oss_dtype io, const void *h, void *out, int B, size_t n, int64_t hsb, hipStream_t s) {
-    if (B > 65535) return OSS_ERR_SHAPE;
-    dim3 grid((unsigned)((n + 2047) / 2048), B);
-    switch (io) {
-        case OSS_F32: hipLaunchKernelGGL(oss_gelu_gate_fwd_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(h), reinterpret_cast<float *>(out), n, hsb); break;
-        case OSS_F16: hipLaunchKernelGGL(oss_gelu_gate_fwd_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(h), reinterpret_cast<f16_t *>(out), n, hsb); break;
-        case OSS_BF16: hipLaunchKernelGGL(oss_gelu_gate_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(h), reinterpret_cast<bf16_t *>(out), n, hsb); break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (B > 65535) return OSS_ERR_SHAPE;
+        hipLaunchKernelGGL(oss_gelu_gate_fwd_kernel<T>, dim3((unsigned)((n + 2047) / 2048), B), dim3(256), 0, s,
+                           reinterpret_cast<const T *>(h), reinterpret_cast<T *>(out), n, hsb);
+        return (int)hipGetLastError();
+    });
 }
 
 int gelu_gate_bwd(oss_dtype io, const void *h, const void *dout, void *dh, int B, size_t n, int64_t hsb, int64_t gsb, hipStream_t s) {
-    if (B > 65535) return OSS_ERR_SHAPE;
-    dim3 grid((unsigned)((n + 2047) / 2048), B);
-    switch (io) {
-        case OSS_F32: hipLaunchKernelGGL(oss_gelu_gate_bwd_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(h), reinterpret_cast<const float *>(dout), reinterpret_cast<float *>(dh), n, hsb, gsb); break;
-        case OSS_F16: hipLaunchKernelGGL(oss_gelu_gate_bwd_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(h), reinterpret_cast<const f16_t *>(dout), reinterpret_cast<f16_t *>(dh), n, hsb, gsb); break;
-        case OSS_BF16: hipLaunchKernelGGL(oss_gelu_gate_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(h), reinterpret_cast<const bf16_t *>(dout), reinterpret_cast<bf16_t *>(dh), n, hsb, gsb); break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (B > 65535) return OSS_ERR_SHAPE;
+        hipLaunchKernelGGL(oss_gelu_gate_bwd_kernel<T>, dim3((unsigned)((n + 2047) / 2048), B), dim3(256), 0, s,
+                           reinterpret_cast<const T *>(h), reinterpret_cast<const T *>(dout), reinterpret_cast<T *>(dh), n, hsb, gsb);
+        return (int)hipGetLastError();
+    });
 }
 
 }  // namespace oss

@@ -10,6 +10,23 @@ namespace oss {
 struct bf16_t;
 struct f16_t;
 
+// The one decoder of oss_dtype.  io_dispatch<S>(io, f) calls f(IoTag<T>{}) with T = float / f16_t / bf16_t for the element types
+// the set S holds and returns what f returns; every other value -- OSS_F32_BF16X3 (a selector of the six GEMM-shaped entry
+// points, which turn it into OSS_F32 + a flag first) and anything out of range -- is OSS_ERR_SHAPE before f runs.  A launcher
+// writes `[&](auto tag) { using T = typename decltype(tag)::type; ... }`; only the types of S are instantiated.
+template <typename T> struct IoTag { using type = T; };
+enum IoSet { IO_ALL, IO_16 };   // all three element types, or the two 16-bit ones
+template <IoSet S = IO_ALL, typename F> int io_dispatch(oss_dtype io, F &&f) {
+    switch ((int)io) {
+        case OSS_F32: if constexpr (S == IO_ALL) return f(IoTag<float>{}); else break;
+        case OSS_F16: return f(IoTag<f16_t>{});
+        case OSS_BF16: return f(IoTag<bf16_t>{});
+    }
+    return OSS_ERR_SHAPE;
+}
+template <IoSet S = IO_ALL> bool io_ok(oss_dtype io) { return io_dispatch<S>(io, [](auto) { return 0; }) == 0; }   // the *_ok predicates
+inline int io_bytes(oss_dtype io) { return io == OSS_F32 ? 4 : io_ok<IO_16>(io) ? 2 : 0; }   // element size; 0: not an element type
+
 // Dynamic LDS above the 48 KiB default has to be enabled per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).
 // One gate per kernel instantiation: what has been enabled so far, one lock-free slot per device, so that a process driving
 // several GPUs (or several host threads) never launches with a stale assumption.

@@ -442,17 +442,18 @@ static int ln_bwd_t(const void *x, const float *w, const float *bias, const void
     return (int)hipGetLastError();
 }
 
+// xt: the type of x / dx, yt: of gate / y / dy.  Built: every pair with an fp32 side, and one 16-bit type on both sides.
 #define OSS_LN_DISPATCH(FN, ...)                                                        \
-    switch ((int)xt * 3 + (int)yt) {                                                    \
-        case 0: return FN<float, float>(__VA_ARGS__);                                   \
-        case 1: return FN<float, f16_t>(__VA_ARGS__);                                   \
-        case 2: return FN<float, bf16_t>(__VA_ARGS__);                                  \
-        case 3: return FN<f16_t, float>(__VA_ARGS__);                                   \
-        case 4: return FN<f16_t, f16_t>(__VA_ARGS__);                                   \
-        case 6: return FN<bf16_t, float>(__VA_ARGS__);                                  \
-        case 8: return FN<bf16_t, bf16_t>(__VA_ARGS__);                                 \
-        default: return OSS_ERR_SHAPE;                                                  \
-    }
+    return io_dispatch(xt, [&](auto tx) {                                               \
+        return io_dispatch(yt, [&](auto ty) {                                           \
+            using TX = typename decltype(tx)::type;                                     \
+            using TY = typename decltype(ty)::type;                                     \
+            if constexpr (sizeof(TX) == 4 || sizeof(TY) == 4 || std::is_same_v<TX, TY>) \
+                return FN<TX, TY>(__VA_ARGS__);                                         \
+            else                                                                        \
+                return OSS_ERR_SHAPE;                                                   \
+        });                                                                             \
+    });
 
 int ln_nchw_fwd(oss_dtype xt, oss_dtype yt, const void *x, const float *w, const float *bias, const void *gate, void *y,
                 float *mean, float *rstd, int B, int C, int P, int64_t xsb, int64_t xsc, int64_t gsb, int64_t gsc, float eps,

@@ -112,21 +112,19 @@ oss_merge4_pair_kernel(const T *__restrict__ out, float *__restrict__ y, int D, 
 }
 
 int merge4(oss_dtype io, const void *out, float *y, int B, int D, int H, int W, hipStream_t s) {
-    if (io != OSS_F32 && H >= 64 && W >= 64 && H % 2 == 0 && W % 2 == 0 &&
-        (reinterpret_cast<uintptr_t>(out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(y) & 7u) == 0) {
-        dim3 grid64((W + 63) / 64, (H + 63) / 64, B * D);
-        if (io == OSS_F16) hipLaunchKernelGGL(oss_merge4_pair_kernel<f16_t>, grid64, dim3(256), 0, s, reinterpret_cast<const f16_t *>(out), y, D, H, W);
-        else               hipLaunchKernelGGL(oss_merge4_pair_kernel<bf16_t>, grid64, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(out), y, D, H, W);
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const T *o = reinterpret_cast<const T *>(out);
+        if constexpr (sizeof(T) == 2) {
+            if (H >= 64 && W >= 64 && H % 2 == 0 && W % 2 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
+                (reinterpret_cast<uintptr_t>(y) & 7u) == 0) {
+                hipLaunchKernelGGL(oss_merge4_pair_kernel<T>, dim3((W + 63) / 64, (H + 63) / 64, B * D), dim3(256), 0, s, o, y, D, H, W);
+                return (int)hipGetLastError();
+            }
+        }
+        hipLaunchKernelGGL(oss_merge4_kernel<T>, dim3((W + 31) / 32, (H + 31) / 32, B * D), dim3(256), 0, s, o, y, D, H, W);
         return (int)hipGetLastError();
-    }
-    dim3 grid((W + 31) / 32, (H + 31) / 32, B * D);
-    switch (io) {
-        case OSS_F32: hipLaunchKernelGGL(oss_merge4_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(out), y, D, H, W); break;
-        case OSS_F16: hipLaunchKernelGGL(oss_merge4_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(out), y, D, H, W); break;
-        case OSS_BF16: hipLaunchKernelGGL(oss_merge4_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(out), y, D, H, W); break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    });
 }
 
 }  // namespace oss

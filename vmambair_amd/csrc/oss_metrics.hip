@@ -225,7 +225,7 @@ oss_image_metrics_finish_kernel(const double *__restrict__ part, double *__restr
 static inline int met_tiles(int n, int tile) { return (n + tile - 1) / tile; }
 
 int image_metrics_ok(oss_dtype io, int C, int H, int W, int crop, int flags) {
-    if (io != OSS_F32 && io != OSS_F16 && io != OSS_BF16) return 0;
+    if (!io_ok(io)) return 0;
     if ((C != 1 && C != 3) || (flags & ~(OSS_METRIC_QUANTISE | OSS_METRIC_Y | OSS_METRIC_REPLICATE))) return 0;
     if ((flags & OSS_METRIC_Y) && C != 3) return 0;
     if (H <= 0 || W <= 0 || crop < 0 || 2 * (int64_t)crop >= H || 2 * (int64_t)crop >= W) return 0;
@@ -270,11 +270,11 @@ int image_metrics(oss_dtype io, const void *a, const void *b, double *out, doubl
     for (int i = 0; i <= 2 * kMetR; ++i) p.g[i] /= sum;
     p.c1 = (0.01 * 255) * (0.01 * 255), p.c2 = (0.03 * 255) * (0.03 * 255);
     const dim3 grid(met_tiles(p.Wo, kMetTW), met_tiles(p.Ho, kMetTH), B * K);
-    if (io == OSS_F32) met_launch<float>(p, flags, grid, s);
-    else if (io == OSS_F16) met_launch<f16_t>(p, flags, grid, s);
-    else met_launch<bf16_t>(p, flags, grid, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    const int e = io_dispatch(io, [&](auto tag) {
+        met_launch<typename decltype(tag)::type>(p, flags, grid, s);
+        return (int)hipGetLastError();
+    });
+    if (e != 0) return e;
     const double pixels = (double)K * p.Hc * p.Wc, windows = (double)K * p.Ho * p.Wo;
     hipLaunchKernelGGL(oss_image_metrics_finish_kernel, dim3(B), dim3(kMetFinish), 0, s, part, out, (size_t)K * grid.x * grid.y, pixels, windows);
     return (int)hipGetLastError();

@@ -792,43 +792,42 @@ static int proj_dgrad_mfma_t(const void *ddts, void *dxdbl, const void *du, cons
 
 // 16-bit I/O and shapes the register-resident operands cover -> matrix-core path
 bool proj_mfma_ok(oss_dtype io, int B, int D, int C, int R, int L) {
-    return io != OSS_F32 && L % 2 == 0 && D <= 16 * 48 && 2 * C <= 16 * 16 && R <= 32 && B <= 65535 && g_proj_force_valu == 0;
+    return io_ok<IO_16>(io) && L % 2 == 0 && D <= 16 * 48 && 2 * C <= 16 * 16 && R <= 32 && B <= 65535 && g_proj_force_valu == 0;
 }
 
 int proj_fwd(oss_dtype io, const void *x2, const float *Wx, const float *Wdt, void *xdbl, void *dts, int B, int D, int C, int R,
              int L, hipStream_t s, int f32_split) {
-    if (!dts && !proj_mfma_ok(io, B, D, C, R, L)) return OSS_ERR_NULL;   // dts may be omitted on the matrix-core path only
-    if (proj_mfma_ok(io, B, D, C, R, L))
-        return io == OSS_BF16 ? proj_fwd_mfma_t<bf16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s)
-                              : proj_fwd_mfma_t<f16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
-    if (io == OSS_F32 && dts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {x2, xdbl, dts}))   // (round 4) fp32 matrix cores
-        return proj_fwd_f32(reinterpret_cast<const float *>(x2), Wx, Wdt, reinterpret_cast<float *>(xdbl), reinterpret_cast<float *>(dts),
-                            B, D, C, R, L, s, f32_split);
-    switch (io) {
-        case OSS_F32: return proj_fwd_t<float>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
-        case OSS_F16: return proj_fwd_t<f16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
-        case OSS_BF16: return proj_fwd_t<bf16_t>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
-        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
-    }
-    return OSS_ERR_SHAPE;
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const bool mfma = proj_mfma_ok(io, B, D, C, R, L);
+        if (!dts && !mfma) return OSS_ERR_NULL;   // dts may be omitted on the matrix-core path only
+        if constexpr (sizeof(T) == 2) {
+            if (mfma) return proj_fwd_mfma_t<T>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
+        } else {
+            if (dts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {x2, xdbl, dts}))   // (round 4) fp32 matrix cores
+                return proj_fwd_f32(reinterpret_cast<const float *>(x2), Wx, Wdt, reinterpret_cast<float *>(xdbl),
+                                    reinterpret_cast<float *>(dts), B, D, C, R, L, s, f32_split);
+        }
+        return proj_fwd_t<T>(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L, s);
+    });
 }
 
 int proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, const float *Wx, const float *Wdt, void *dx2, int B,
                int D, int C, int R, int L, hipStream_t s, int f32_split) {
-    if (!ddts && !proj_mfma_ok(io, B, D, C, R, L)) return OSS_ERR_NULL;
-    if (proj_mfma_ok(io, B, D, C, R, L))
-        return io == OSS_BF16 ? proj_dgrad_mfma_t<bf16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s)
-                              : proj_dgrad_mfma_t<f16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
-    if (io == OSS_F32 && ddts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {ddts, dxdbl, du, dx2}))
-        return proj_dgrad_f32(reinterpret_cast<const float *>(ddts), reinterpret_cast<float *>(dxdbl), reinterpret_cast<const float *>(du),
-                              Wx, Wdt, reinterpret_cast<float *>(dx2), B, D, C, R, L, s, f32_split);
-    switch (io) {
-        case OSS_F32: return proj_dgrad_t<float>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
-        case OSS_F16: return proj_dgrad_t<f16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
-        case OSS_BF16: return proj_dgrad_t<bf16_t>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
-        case OSS_F32_BF16X3: break;   // a selector of the six GEMM-shaped entry points, not an element type
-    }
-    return OSS_ERR_SHAPE;
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const bool mfma = proj_mfma_ok(io, B, D, C, R, L);
+        if (!ddts && !mfma) return OSS_ERR_NULL;
+        if constexpr (sizeof(T) == 2) {
+            if (mfma) return proj_dgrad_mfma_t<T>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
+        } else {
+            if (ddts && !g_proj_force_valu && proj_f32_ok(B, D, C, R, L, {ddts, dxdbl, du, dx2}))
+                return proj_dgrad_f32(reinterpret_cast<const float *>(ddts), reinterpret_cast<float *>(dxdbl),
+                                      reinterpret_cast<const float *>(du), Wx, Wdt, reinterpret_cast<float *>(dx2), B, D, C, R, L, s,
+                                      f32_split);
+        }
+        return proj_dgrad_t<T>(ddts, dxdbl, du, Wx, Wdt, dx2, B, D, C, R, L, s);
+    });
 }
 
 void proj_force_valu(int on) { g_proj_force_valu = on ? 1 : 0; }
@@ -921,43 +920,35 @@ static int cross_scan2_t(const void *x, void *x2, int B, int D, int H, int W, in
 
 int cross_scan2(oss_dtype it, oss_dtype ot, const void *x, void *x2, int B, int D, int H, int W, int64_t xsb, int64_t xsc,
                 hipStream_t s) {
-    if (B > 65535 || D > 65535) return OSS_ERR_SHAPE;
-    switch ((int)it * 3 + (int)ot) {
-        case 0: return cross_scan2_t<float, float>(x, x2, B, D, H, W, xsb, xsc, s);
-        case 1: return cross_scan2_t<float, f16_t>(x, x2, B, D, H, W, xsb, xsc, s);
-        case 2: return cross_scan2_t<float, bf16_t>(x, x2, B, D, H, W, xsb, xsc, s);
-        case 4: return cross_scan2_t<f16_t, f16_t>(x, x2, B, D, H, W, xsb, xsc, s);
-        case 8: return cross_scan2_t<bf16_t, bf16_t>(x, x2, B, D, H, W, xsb, xsc, s);
-        default: return OSS_ERR_SHAPE;
-    }
+    return io_dispatch(it, [&](auto ti) {
+        return io_dispatch(ot, [&](auto to) {
+            using TI = typename decltype(ti)::type;
+            using TO = typename decltype(to)::type;
+            if constexpr (sizeof(TI) == 4 || std::is_same_v<TI, TO>) {   // fp32 to any type, or a 16-bit type to itself
+                if (B > 65535 || D > 65535) return OSS_ERR_SHAPE;
+                return cross_scan2_t<TI, TO>(x, x2, B, D, H, W, xsb, xsc, s);
+            }
+            return OSS_ERR_SHAPE;
+        });
+    });
 }
 
 int cross_merge2(oss_dtype io, const void *g2, void *dx, int B, int D, int H, int W, hipStream_t s) {
-    if (B > 65535 || D > 65535) return OSS_ERR_SHAPE;
-    if (io != OSS_F32 && H >= 64 && W >= 64 && H % 2 == 0 && W % 2 == 0 &&
-        ((reinterpret_cast<uintptr_t>(g2) | reinterpret_cast<uintptr_t>(dx)) & 3u) == 0) {
-        dim3 grid64(((H + 63) / 64) * ((W + 63) / 64), D, B);
-        if (io == OSS_F16) hipLaunchKernelGGL(oss_cross_merge2_pair_kernel<f16_t>, grid64, dim3(256), 0, s, reinterpret_cast<const f16_t *>(g2), reinterpret_cast<f16_t *>(dx), D, H, W);
-        else               hipLaunchKernelGGL(oss_cross_merge2_pair_kernel<bf16_t>, grid64, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(g2), reinterpret_cast<bf16_t *>(dx), D, H, W);
+    return io_dispatch(io, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (B > 65535 || D > 65535) return OSS_ERR_SHAPE;
+        const T *g = reinterpret_cast<const T *>(g2);
+        T *o = reinterpret_cast<T *>(dx);
+        if constexpr (sizeof(T) == 2) {
+            if (H >= 64 && W >= 64 && H % 2 == 0 && W % 2 == 0 &&
+                ((reinterpret_cast<uintptr_t>(g2) | reinterpret_cast<uintptr_t>(dx)) & 3u) == 0) {
+                hipLaunchKernelGGL(oss_cross_merge2_pair_kernel<T>, dim3(((H + 63) / 64) * ((W + 63) / 64), D, B), dim3(256), 0, s, g, o, D, H, W);
+                return (int)hipGetLastError();
+            }
+        }
+        hipLaunchKernelGGL(oss_cross_merge2_kernel<T>, dim3(((H + 31) / 32) * ((W + 31) / 32), D, B), dim3(256), 0, s, g, o, D, H, W);
         return (int)hipGetLastError();
-    }
-    dim3 grid(((H + 31) / 32) * ((W + 31) / 32), D, B);
-    switch (io) {
-        case OSS_F32:
-            hipLaunchKernelGGL(oss_cross_merge2_kernel<float>, grid, dim3(256), 0, s, reinterpret_cast<const float *>(g2),
-                               reinterpret_cast<float *>(dx), D, H, W);
-            break;
-        case OSS_F16:
-            hipLaunchKernelGGL(oss_cross_merge2_kernel<f16_t>, grid, dim3(256), 0, s, reinterpret_cast<const f16_t *>(g2),
-                               reinterpret_cast<f16_t *>(dx), D, H, W);
-            break;
-        case OSS_BF16:
-            hipLaunchKernelGGL(oss_cross_merge2_kernel<bf16_t>, grid, dim3(256), 0, s, reinterpret_cast<const bf16_t *>(g2),
-                               reinterpret_cast<bf16_t *>(dx), D, H, W);
-            break;
-        default: return OSS_ERR_SHAPE;
-    }
-    return (int)hipGetLastError();
+    });
 }
 
 }  // namespace oss
