@@ -350,6 +350,42 @@ int oss_conv1x1_fwd(oss_dtype io, const void *x, const float *weight, const floa
 int oss_conv1x1_dgrad(oss_dtype io, const void *dy, const float *weight, void *dx, int batch, int cout, int cin, int pixels,
                       int64_t dy_batch_stride, int64_t dy_channel_stride, oss_stream_t stream);
 size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels);
+/* Pre-packed 16-bit weight images of oss_conv1x1_fwd / oss_conv1x1_dgrad.  The weights change once per optimizer step, yet every
+ * wave of every launch narrows the fp32 matrix again; an IMAGE holds the matrix operand of one direction already narrowed to the
+ * io type (the loaders' round-to-nearest-even), zero-padded to whole tiles and in MFMA fragment order.  For the (M x K) product
+ * operand W(m, k), KSTEPS = ceil(K / 16), tile t < ceil(M / 32), k-step s < KSTEPS, lane l < 64, e < 8:
+ *   image[((t * KSTEPS + s) * 64 + l) * 8 + e] = W(32 t + (l & 31), 16 s + 8 (l >> 5) + e)      (0 outside M x K)
+ *   forward image:        M = cout, K = cin,  W(m, k) = weight[m * cin + k]
+ *   input-gradient image: M = cin,  K = cout, W(m, k) = weight[k * cin + m]
+ * i.e. ceil(M / 32) * ceil(K / 16) * 1024 bytes each (oss_conv1x1_fwd_image_bytes / _dgrad_image_bytes), 16-byte aligned.
+ * oss_conv1x1_pack_weights writes the images of MANY weights in one launch from a table in DEVICE memory of
+ * oss_conv1x1_pack_row_bytes() bytes per row; oss_conv1x1_pack_fill (host only, no GPU work) writes the
+ * oss_conv1x1_pack_rows(cout, cin) rows of ONE weight and both of its images into host memory and returns their number (< 0: an
+ * error code); the caller concatenates the rows of all weights and copies them to the device once.  The launch reads the
+ * table and the weights when it RUNS: no host synchronisation, capturable into a hipGraph, replays repack from the live weights.
+ * The images are only as current as the last pack launch: whoever changes a weight must pack again before the next _packed call.
+ *   oss_conv1x1_fwd_packed / oss_conv1x1_dgrad_packed: oss_conv1x1_fwd / _dgrad with the image of their direction.  The pixel-pair
+ *   kernels (even pixel count, 4-byte aligned tensors) and the workgroup-level kernels then fetch their weight fragments from the
+ *   image -- same products added in the same order, results bit-identical to the fp32-weight call; the remaining kernel forms
+ *   (odd pixel counts, unaligned tensors) read `weight` as before.
+ *   oss_ln_conv1x1_fwd_packed (forward image): the same for the LayerNorm-fused forward declared below; shapes and every other
+ *   argument as there.  (oss_conv1x1_dgrad_ln_bwd has no packed form: it measured no gain.)
+ *   image == NULL or io == OSS_F32 / OSS_F32_BF16X3: exactly the unpacked entry point. */
+size_t oss_conv1x1_fwd_image_bytes(int cout, int cin);
+size_t oss_conv1x1_dgrad_image_bytes(int cout, int cin);
+size_t oss_conv1x1_pack_row_bytes(void);
+int oss_conv1x1_pack_rows(int cout, int cin);
+int oss_conv1x1_pack_fill(void *rows, const float *weight, void *fwd_image, void *dgrad_image, int cout, int cin);
+int oss_conv1x1_pack_weights(oss_dtype io, const void *table, int n_rows, oss_stream_t stream);
+int oss_conv1x1_fwd_packed(oss_dtype io, const void *x, const float *weight, const void *fwd_image, const float *bias,
+                           const void *residual, void *y, int batch, int cout, int cin, int pixels, int64_t x_batch_stride,
+                           int64_t x_channel_stride, oss_stream_t stream);
+int oss_conv1x1_dgrad_packed(oss_dtype io, const void *dy, const float *weight, const void *dgrad_image, void *dx, int batch,
+                             int cout, int cin, int pixels, int64_t dy_batch_stride, int64_t dy_channel_stride,
+                             oss_stream_t stream);
+int oss_ln_conv1x1_fwd_packed(oss_dtype io, const void *x, const float *ln_weight, const float *ln_bias, float eps, void *n, float *mean,
+                              float *rstd, const float *weight, const void *fwd_image, const float *bias, void *y, int batch, int cout,
+                              int cin, int pixels, int64_t x_batch_stride, int64_t x_channel_stride, oss_stream_t stream);
 /* Tuning override of oss_conv1x1_wgrad / oss_proj_wgrad: MFMA tiles per wave, 0 = 1 x 1 (default), 12 / 21 / 22 = rows x columns
  * of 32 x 32 tiles (fewer re-reads of the operands, fewer waves).  Same results up to the summation order; the library starts
  * at 0. */
@@ -767,13 +803,13 @@ int oss_f32_matmul_modes(void);
 
 /* ABI guard.  oss_scan_fwd_params / oss_scan_bwd_params / oss_chan_params cross the boundary BY POINTER, so a binding layer
  * compiled against another revision of this header would hand the kernels garbage pointers.  OSS_ABI_VERSION is bumped with
- * every change of a struct or of an entry point's argument list (8: the value OSS_F32_BF16X3 of oss_dtype and
- * oss_f32_matmul_modes(); no struct changed); oss_abi_struct_bytes(which) is the library's own sizeof
+ * every change of a struct or of an entry point's argument list (9: the pre-packed weight images of the 1x1 convolutions,
+ * oss_conv1x1_pack_* and the *_packed entry points; no struct changed); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 8
+#define OSS_ABI_VERSION 9
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

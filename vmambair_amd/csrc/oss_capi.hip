@@ -184,7 +184,7 @@ static const char *const kFamName[FAM_N] = {"conv1x1 forward / input gradient (+
                                             "deferred partial-sum finishing", "Adam(W) + EMA"};
 // substrings of the kernel names a family launches (matched by bench.py against the kernel trace)
 static const char *const kFamKernels[FAM_N] = {"oss_conv1x1_pair_kernel|oss_conv1x1_pairk_kernel|oss_conv1x1_pairw_kernel|oss_conv1x1_wg_kernel|"
-                                               "oss_conv1x1_dgrad_lnbwd_kernel|oss_conv1x1_f32_kernel",
+                                               "oss_conv1x1_dgrad_lnbwd_kernel|oss_conv1x1_f32_kernel|oss_conv1x1_pack_kernel",
                                                "oss_conv1x1_wgrad|oss_rows_f32_wgrad|oss_proj_wgrad",
                                                "oss_dwconv3x3|oss_dwgate|oss_effn",
                                                "oss_proj_fwd|oss_proj_dgrad|oss_dt_fwd|oss_dt_dgrad|oss_proj_valu",
@@ -476,6 +476,47 @@ int oss_conv1x1_dgrad(oss_dtype io, const void *dy, const float *weight, void *d
     return conv1x1(io, dy, weight, nullptr, dx, batch, cin, cout, pixels, gsb, gsc, 1, cin, reinterpret_cast<hipStream_t>(stream), nullptr, x3);
 }
 
+// ---- pre-packed 16-bit weight images (oss_conv1x1.hip) ----
+size_t oss_conv1x1_fwd_image_bytes(int cout, int cin) { return cout > 0 && cin > 0 ? conv1x1_image_bytes(cout, cin) : 0; }
+size_t oss_conv1x1_dgrad_image_bytes(int cout, int cin) { return cout > 0 && cin > 0 ? conv1x1_image_bytes(cin, cout) : 0; }
+size_t oss_conv1x1_pack_row_bytes(void) { return conv1x1_pack_row_bytes(); }
+int oss_conv1x1_pack_rows(int cout, int cin) { return cout > 0 && cin > 0 ? conv1x1_pack_rows(cout, cin) : 0; }
+int oss_conv1x1_pack_fill(void *rows, const float *weight, void *fwd_image, void *dgrad_image, int cout, int cin) {
+    if (!rows || !weight || !fwd_image || !dgrad_image) return OSS_ERR_NULL;
+    if (cout <= 0 || cin <= 0 || (size_t)cout * cin >= (1u << 30)) return OSS_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(fwd_image) | reinterpret_cast<uintptr_t>(dgrad_image)) & 15u) return OSS_ERR_SHAPE;
+    return conv1x1_pack_fill(rows, weight, fwd_image, dgrad_image, cout, cin);
+}
+int oss_conv1x1_pack_weights(oss_dtype io, const void *table, int n_rows, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    fam_count(FAM_CONV1X1, (double)n_rows * 256.0 * 16.0 * 3.0);   // each piece: 16 bytes written, 32 bytes of fp32 read
+    if (!table) return OSS_ERR_NULL;
+    if (n_rows <= 0) return OSS_ERR_SHAPE;
+    return conv1x1_pack(io, table, n_rows, reinterpret_cast<hipStream_t>(stream));
+}
+// image == NULL or fp32 I/O: exactly oss_conv1x1_fwd / oss_conv1x1_dgrad
+int oss_conv1x1_fwd_packed(oss_dtype io, const void *x, const float *weight, const void *fwd_image, const float *bias,
+                           const void *residual, void *y, int batch, int cout, int cin, int pixels, int64_t xsb, int64_t xsc,
+                           oss_stream_t stream) {
+    if (!fwd_image || !io_ok<IO_16>(io)) return oss_conv1x1_fwd(io, x, weight, bias, residual, y, batch, cout, cin, pixels, xsb, xsc, stream);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * io_bytes(io) * ((double)cin + cout + (residual ? cout : 0)) + 2.0 * cin * cout);
+    if (!x || !weight || !y) return OSS_ERR_NULL;
+    if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535 || cout > 32 * 65535) return OSS_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(fwd_image) & 15u) return OSS_ERR_SHAPE;
+    return conv1x1(io, x, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, cin, 1, reinterpret_cast<hipStream_t>(stream),
+                   residual, 0, fwd_image);
+}
+int oss_conv1x1_dgrad_packed(oss_dtype io, const void *dy, const float *weight, const void *dgrad_image, void *dx, int batch,
+                             int cout, int cin, int pixels, int64_t gsb, int64_t gsc, oss_stream_t stream) {
+    if (!dgrad_image || !io_ok<IO_16>(io)) return oss_conv1x1_dgrad(io, dy, weight, dx, batch, cout, cin, pixels, gsb, gsc, stream);
+    fam_count(FAM_CONV1X1, (double)batch * pixels * io_bytes(io) * ((double)cin + cout) + 2.0 * cin * cout);
+    if (!dy || !weight || !dx) return OSS_ERR_NULL;
+    if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535) return OSS_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(dgrad_image) & 15u) return OSS_ERR_SHAPE;
+    return conv1x1(io, dy, weight, nullptr, dx, batch, cin, cout, pixels, gsb, gsc, 1, cin, reinterpret_cast<hipStream_t>(stream), nullptr, 0,
+                   dgrad_image);
+}
+
 size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels) {
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0) return 0;
     return (size_t)batch * conv1x1_wgrad_slabs(pixels) * cout * (cin + 1);  // + 1: the dbias column
@@ -548,6 +589,19 @@ int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, cons
     if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
     return ln_conv1x1_wg(io, x, ln_weight, ln_bias, eps, n, mean, rstd, weight, bias, y, batch, cout, cin, pixels, xsb, xsc,
                          reinterpret_cast<hipStream_t>(stream));
+}
+
+int oss_ln_conv1x1_fwd_packed(oss_dtype io, const void *x, const float *ln_weight, const float *ln_bias, float eps, void *n, float *mean,
+                              float *rstd, const float *weight, const void *fwd_image, const float *bias, void *y, int batch, int cout,
+                              int cin, int pixels, int64_t xsb, int64_t xsc, oss_stream_t stream) {
+    if (!fwd_image)
+        return oss_ln_conv1x1_fwd(io, x, ln_weight, ln_bias, eps, n, mean, rstd, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, stream);
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    fam_count(FAM_CONV1X1, (double)batch * pixels * (io_bytes(io) * (2.0 * cin + cout) + 8.0) + 2.0 * cin * cout);
+    if (!x || !ln_weight || !n || !mean || !rstd || !weight || !y) return OSS_ERR_NULL;
+    if (batch <= 0 || batch > 65535) return OSS_ERR_SHAPE;
+    return ln_conv1x1_wg(io, x, ln_weight, ln_bias, eps, n, mean, rstd, weight, bias, y, batch, cout, cin, pixels, xsb, xsc,
+                         reinterpret_cast<hipStream_t>(stream), fwd_image);
 }
 
 int oss_conv1x1_dgrad_ln_bwd_ok(oss_dtype io, int cout, int cin, int pixels, int batch) {

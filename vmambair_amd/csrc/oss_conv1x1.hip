@@ -338,10 +338,15 @@ __device__ __forceinline__ void wflat_frags(const WRaw<KS> &r, T *__restrict__ m
 // group is issued before the activation loads.  The first version fetched weights k-step by k-step and bias / residual row
 // by row, each behind its own s_waitcnt vmcnt(0) (which on gfx9 also waits for the previous row's store): 12 row tiles on
 // one wave took 36 us (profiles/r02_conv1x1_pipeline.txt).
-template <typename T, int KS, bool WT, bool WVEC, bool RES, bool PF>
+//
+// WIMG: the weights come from a pre-packed image in MFMA fragment order (oss_conv1x1_pack_kernel below): tile mt, k-step ks is
+// ONE coalesced 16-byte load per lane, already narrowed and zero-padded -- no conversion, no mask, 4 raw registers per k-step
+// instead of 8 (so PF also fits KS = 8).  WT / WVEC are ignored; `w` stays a readable address for the bias stand-in.
+template <typename T, int KS, bool WT, bool WVEC, bool RES, bool PF, bool WIMG = false>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_pair_kernel(const T *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
-                        T *__restrict__ y, int M, int K, int P, int64_t xsb, int xsk, int mt_per_wave, const T *__restrict__ res) {
+                        T *__restrict__ y, int M, int K, int P, int64_t xsb, int xsk, int mt_per_wave, const T *__restrict__ res,
+                        const u32x4 *__restrict__ wimg = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int p0 = (blockIdx.x * 4 + wave) * 64;
@@ -361,16 +366,20 @@ oss_conv1x1_pair_kernel(const T *__restrict__ x, const float *__restrict__ w, co
     const int mt_begin = blockIdx.z * mt_per_wave, mt_end = min(mt_total, mt_begin + mt_per_wave);
     if (mt_begin >= mt_end) return;
 
-    constexpr bool WLDS = !WT && WVEC;   // forward weights through LDS (see wflat_issue)
+    constexpr bool WLDS = !WIMG && !WT && WVEC;   // forward weights through LDS (see wflat_issue)
     __shared__ __attribute__((aligned(16))) T wlds[WLDS ? 4 * 32 * (16 * KS + 8) : 8];
     T *myl = wlds + (WLDS ? wave * 32 * (16 * KS + 8) : 0);
     const int wf_row0 = WLDS ? (4 * lane) / K : 0, wf_k0 = WLDS ? (4 * lane) % K : 0, wf_sr = WLDS ? 256 / K : 0, wf_sk = WLDS ? 256 % K : 0;
-    WRaw<KS> wr;
+    WRaw<WIMG ? 1 : KS> wr;
+    u32x4 wq[WIMG ? KS : 1];
     float bl;
     uint32_t rw[16];
     auto issue = [&](int mt) {   // one tile's operand group
         const int m0 = mt * 32;
-        if constexpr (WLDS) wflat_issue<KS>(wr, w, m0, M, K, lane);
+        if constexpr (WIMG) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) wq[ks] = wimg[((size_t)mt * ksteps + min(ks, ksteps - 1)) * 64 + lane];
+        } else if constexpr (WLDS) wflat_issue<KS>(wr, w, m0, M, K, lane);
         else                wraw_issue<KS, WT, WVEC>(wr, w, m0 + col, M, K, kg);
         bl = bp[min(m0 + col, M - 1)];
         if constexpr (RES) {
@@ -398,7 +407,10 @@ oss_conv1x1_pair_kernel(const T *__restrict__ x, const float *__restrict__ w, co
     for (int mt = mt_begin; mt < mt_end; ++mt) {
         const int m0 = mt * 32;
         s16x8 af[KS];
-        if constexpr (WLDS) wflat_frags<T, KS>(wr, myl, af, m0, M, K, col, kg, wf_row0, wf_k0, wf_sr, wf_sk);
+        if constexpr (WIMG) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) af[ks] = __builtin_bit_cast(s16x8, wq[ks]);
+        } else if constexpr (WLDS) wflat_frags<T, KS>(wr, myl, af, m0, M, K, col, kg, wf_row0, wf_k0, wf_sr, wf_sk);
         else                wraw_narrow<T, KS, WT, WVEC>(wr, af, m0 + col, M, K, kg);
         const float bcur = bias ? bl : 0.f;
         uint32_t rcur[16];
@@ -550,10 +562,12 @@ oss_conv1x1_pairw_kernel(const T *__restrict__ x, const float *__restrict__ w, c
 // K is walked in chunks of KS k-steps (KS * 16 channels) whose activation fragments live in registers; up to MT
 // output row tiles per workgroup are accumulated across the chunks, so any K and M are covered by one kernel
 // (grid.z splits M into groups of <= MT tiles).
-template <typename T, int KS, int MT, bool WT, bool WVEC>
+// WIMG: weight fragments from the pre-packed image (see oss_conv1x1_pair_kernel): KS coalesced 16-byte loads per chunk and tile.
+template <typename T, int KS, int MT, bool WT, bool WVEC, bool WIMG = false>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_pairk_kernel(const T *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
-                        T *__restrict__ y, int M, int K, int P, int64_t xsb, int xsk, const T *__restrict__ res) {
+                        T *__restrict__ y, int M, int K, int P, int64_t xsb, int xsk, const T *__restrict__ res,
+                        const u32x4 *__restrict__ wimg = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.y;
     const int p0 = (blockIdx.x * 4 + wave) * 64;
@@ -588,8 +602,16 @@ oss_conv1x1_pairk_kernel(const T *__restrict__ x, const float *__restrict__ w, c
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
             s16x8 af[KS];   // the tile's weight fragments of this chunk, fetched together (rows / columns outside the matrix: zeros)
+            if constexpr (WIMG) {
+                // (a tile or k-step outside the image: the address is clamped into it, the guards below skip its MFMAs)
+                const int ksteps = (K + 15) >> 4;
+                const u32x4 *wt_ = wimg + (size_t)min(mt0 + t, ((M + 31) >> 5) - 1) * ksteps * 64 + lane;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) af[ks] = load_wfrag<T, WT, WVEC>(w, (mt0 + t) * 32 + col, M, K, kc + ks * 16 + kg * 8);
+                for (int ks = 0; ks < KS; ++ks) af[ks] = __builtin_bit_cast(s16x8, wt_[(size_t)min((kc >> 4) + ks, ksteps - 1) * 64]);
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) af[ks] = load_wfrag<T, WT, WVEC>(w, (mt0 + t) * 32 + col, M, K, kc + ks * 16 + kg * 8);
+            }
             if ((mt0 + t) * 32 < M) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
@@ -835,9 +857,12 @@ oss_conv1x1_wgrad_finish(const float *__restrict__ part, float *__restrict__ dw,
 // 1024 / 2048 / 4096: 177.0 / 176.2 / 175.0 images/s (profiles/r02_conv1x1_pipeline.txt)
 constexpr long kConv1x1TargetWaves = 1024;
 
+// wimg: the pre-packed image of W for THIS direction (conv1x1_pack_fill), or NULL.  It only changes where the pixel-pair kernels
+// (and the workgroup-level ones of oss_conv1x1_wg.hip) fetch their weight fragments; the shapes those kernels do not take read
+// the fp32 weights as before.
 template <typename T>
 static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, int B, int M, int K, int P, int64_t xsb,
-                           int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const T *res) {
+                           int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const T *res, const void *wimg = nullptr) {
     const int pblocks = (P + 127) / 128, mt = (M + 31) / 32;
     const bool wt = (ws_m == 1 && ws_k == M);          // input gradient: weights read transposed
     const bool plain = (ws_k == 1 && ws_m == K);
@@ -849,7 +874,8 @@ static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, 
         const int pb = (P + 255) / 256;
         const long waves_p = (long)B * ((P + 63) / 64);
         const int xk = (int)xsk;
-        if (plain && !wvec && K > 16 * 3 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0) {
+        const u32x4 *img = reinterpret_cast<const u32x4 *>(wimg);
+        if (!img && plain && !wvec && K > 16 * 3 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0) {
             // forward with rows that are not 16-byte aligned (K = 127, the EFFN hidden width at dim 48): weight tile through LDS
             hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
             return;
@@ -864,27 +890,39 @@ static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, 
 #define OSS_PAIR2(KS_, WT_, WV_, PF_) do { if (res) hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, WT_, WV_, true, PF_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res); \
                                            else     hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, WT_, WV_, false, PF_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res); } while (0)
 #define OSS_PAIR(KS_, PF_) do { if (wt) OSS_PAIR2(KS_, true, false, PF_); else if (wvec) OSS_PAIR2(KS_, false, true, PF_); else OSS_PAIR2(KS_, false, false, PF_); } while (0)
-            // PF (next tile's operands in flight during the current tile): the raw fp32 fragments of two tiles fit up to 6 k-steps
-            if (K <= 16 * 3)      OSS_PAIR(3, true);
+#define OSS_PAIRI(KS_, PF_) do { if (res) hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, false, false, true, PF_, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res, img); \
+                                 else     hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, false, false, false, PF_, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res, img); } while (0)
+            // PF (next tile's operands in flight during the current tile): the raw fp32 fragments of two tiles fit up to 6 k-steps,
+            // the 16-bit fragments of an image up to 8
+            if (img) {
+                if (K <= 16 * 3)      OSS_PAIRI(3, true);
+                else if (K <= 16 * 6) OSS_PAIRI(6, true);
+                else if (K <= 16 * 8) OSS_PAIRI(8, true);
+                else                  OSS_PAIRI(12, false);
+            }
+            else if (K <= 16 * 3) OSS_PAIR(3, true);
             else if (K <= 16 * 6) OSS_PAIR(6, true);
             else if (K <= 16 * 8) OSS_PAIR(8, false);    // K = 127 (EFFN hidden width at dim 48): no duplicate k-steps
             else                  OSS_PAIR(12, false);
+#undef OSS_PAIRI
 #undef OSS_PAIR2
 #undef OSS_PAIR
-#undef OSS_PAIR1
         } else {
             // K in chunks of 128: up to 3 row tiles accumulate per workgroup (fewest re-loads that still fill the chip)
             int per = 3;
             while (per > 1 && waves_p * ((mt + per - 1) / per) < 4096) --per;
             if (per > mt) per = mt;
-            if (per == 1 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && plain) {   // forward: weights through LDS
+            if (!img && per == 1 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && plain) {   // forward: weights through LDS
                 hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
                 return;
             }
             dim3 grid(pb, B, (mt + per - 1) / per);
 #define OSS_PAIR1(MT_, WT_, WV_) hipLaunchKernelGGL((oss_conv1x1_pairk_kernel<T, 8, MT_, WT_, WV_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res)
 #define OSS_PAIR(MT_) do { if (wt) OSS_PAIR1(MT_, true, false); else if (wvec) OSS_PAIR1(MT_, false, true); else OSS_PAIR1(MT_, false, false); } while (0)
-            if (per == 1) OSS_PAIR(1); else if (per == 2) OSS_PAIR(2); else OSS_PAIR(3);
+#define OSS_PAIRI(MT_) hipLaunchKernelGGL((oss_conv1x1_pairk_kernel<T, 8, MT_, false, false, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res, img)
+            if (img) { if (per == 1) OSS_PAIRI(1); else if (per == 2) OSS_PAIRI(2); else OSS_PAIRI(3); }
+            else if (per == 1) OSS_PAIR(1); else if (per == 2) OSS_PAIR(2); else OSS_PAIR(3);
+#undef OSS_PAIRI
 #undef OSS_PAIR
 #undef OSS_PAIR1
         }
@@ -920,11 +958,11 @@ static std::atomic<int> g_conv_wg{1};
 void conv1x1_set_wg(int on) { g_conv_wg.store(on ? 1 : 0); }
 
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res, int f32_split) {
+            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res, int f32_split, const void *wimg) {
     {
         const bool wt = (ws_m == 1 && ws_k == M), plain = (ws_k == 1 && ws_m == K);
         if ((wt || plain) && g_conv_wg.load() != 0 && conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res))
-            return conv1x1_wg(io, x, w, bias, y, B, M, K, P, xsb, xsk, wt ? 1 : 0, s, res);
+            return conv1x1_wg(io, x, w, bias, y, B, M, K, P, xsb, xsk, wt ? 1 : 0, s, res, wimg);
     }
     return io_dispatch(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
@@ -933,9 +971,78 @@ int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void
         if constexpr (sizeof(T) == 4) {   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
             return conv1x1_f32(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, f32_split);
         } else {
-            conv1x1_launch<T>(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp);
+            conv1x1_launch<T>(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, wimg);
             return (int)hipGetLastError();
         }
+    });
+}
+
+// ---- pre-packed 16-bit weight images ---------------------------------------------------------------------------------------
+// Between two optimizer steps nothing writes the weights, yet every wave of every forward / input-gradient launch re-read the fp32
+// matrix and narrowed it again (~1500 waves per launch at the headline shapes; the transposed form as 8 separate 4-byte loads, 4
+// conversions and the edge selects per MFMA fragment).  ONE launch per step writes, for every weight of a table, the operand A of
+// both products in MFMA FRAGMENT ORDER, narrowed with the loaders' own rounding and zero-padded to whole tiles:
+//   img[((t * KSTEPS + s) * 64 + l) * 8 + e] = from_f32<T>(W(32 t + (l & 31), 16 s + 8 (l >> 5) + e))     (0 outside M x K)
+// so that lane l's fragment of tile t, k-step s is the 16 bytes at piece (t * KSTEPS + s) * 64 + l: consecutive lanes read
+// consecutive pieces (8 cache lines per load instruction; a row-major 16-bit matrix with a row per lane would touch 64).
+// Table row = 256 consecutive pieces of one image; the pointers are read from the table (oss_global_ptr.h).
+struct PackRow {
+    const float *w;   // (Cout, Cin) fp32, row-major
+    void *img;        // base of the image
+    int M, K;         // the product's rows / depth: forward (Cout, Cin), input gradient (Cin, Cout)
+    int wt;           // 0: W(m, k) = w[m * K + k]; 1: W(m, k) = w[k * M + m]
+    int first;        // first piece of this row's 256
+};
+constexpr int kPackPieces = 256;
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+oss_conv1x1_pack_kernel(const PackRow *__restrict__ rows) {
+    const PackRow r = rows[blockIdx.x];
+    const float *w = table_ptr<const float>(&rows[blockIdx.x].w);
+    u32x4 *img = table_ptr<u32x4>(&rows[blockIdx.x].img);
+    const int ksteps = (r.K + 15) >> 4, total = ((r.M + 31) >> 5) * ksteps * 64;
+    const int q = r.first + (int)threadIdx.x;
+    if (q >= total) return;
+    const int l = q & 63, unit = q >> 6, t = unit / ksteps, s = unit - t * ksteps;
+    const int m = 32 * t + (l & 31), k0 = 16 * s + 8 * (l >> 5);
+    const bool mok = m < r.M;
+    const int mc = mok ? m : 0;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int k = k0 + e;
+        const bool kok = k < r.K;
+        const int kc = kok ? k : r.K - 1;   // clamped address, masked value
+        const float wv = r.wt ? w[(size_t)kc * r.M + mc] : w[(size_t)mc * r.K + kc];
+        v[e] = (mok && kok) ? wv : 0.f;
+    }
+    img[q] = __builtin_bit_cast(u32x4, cvt8<T>(f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]}));
+}
+
+size_t conv1x1_image_bytes(int M, int K) { return (size_t)((M + 31) / 32) * ((K + 15) / 16) * 1024; }
+size_t conv1x1_pack_row_bytes() { return sizeof(PackRow); }
+int conv1x1_pack_rows(int cout, int cin) {
+    const size_t per = (size_t)kPackPieces * 16;
+    return (int)((conv1x1_image_bytes(cout, cin) + per - 1) / per + (conv1x1_image_bytes(cin, cout) + per - 1) / per);
+}
+// host: the table rows of one weight (both images) -> rows written
+int conv1x1_pack_fill(void *rows, const float *w, void *fwd_img, void *dgrad_img, int cout, int cin) {
+    PackRow *out = reinterpret_cast<PackRow *>(rows);
+    int n = 0;
+    for (int dir = 0; dir < 2; ++dir) {
+        const int M = dir ? cin : cout, K = dir ? cout : cin;
+        const int total = (int)(conv1x1_image_bytes(M, K) / 16);
+        for (int first = 0; first < total; first += kPackPieces)
+            out[n++] = PackRow{w, dir ? dgrad_img : fwd_img, M, K, dir, first};
+    }
+    return n;
+}
+int conv1x1_pack(oss_dtype io, const void *table, int n_rows, hipStream_t s) {
+    return io_dispatch<IO_16>(io, [&](auto tag) {
+        hipLaunchKernelGGL(oss_conv1x1_pack_kernel<typename decltype(tag)::type>, dim3(n_rows), dim3(256), 0, s,
+                           reinterpret_cast<const PackRow *>(table));
+        return (int)hipGetLastError();
     });
 }
 

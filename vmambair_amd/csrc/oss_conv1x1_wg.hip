@@ -69,10 +69,14 @@ struct WgLnArgs {
     float eps;
 };
 
-template <typename T, int KS, bool WT, int PT, bool RES, bool PF, bool LN>
+// WIMG: the weight fragments come from the pre-packed image of this direction (oss_conv1x1.hip, oss_conv1x1_pack_kernel): one
+// coalesced 16-byte load per k-step, already narrowed and zero-padded, in place of two 16-byte loads of fp32 (8 four-byte loads
+// when WT) and their conversion.  Same fragments, same order of the k-steps: bit-identical results.
+template <typename T, int KS, bool WT, int PT, bool RES, bool PF, bool LN, bool WIMG = false>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias, T *__restrict__ y,
-                      int M, int P, int64_t xsb, int64_t xsk, const T *__restrict__ res, WgLnArgs<T> ln) {
+                      int M, int P, int64_t xsb, int64_t xsk, const T *__restrict__ res, WgLnArgs<T> ln,
+                      const u32x4 *__restrict__ wimg = nullptr) {
     // LDS row pitches in elements (16-byte aligned rows).  (round 5) Two pitches: profiles/r04_pmc_lds_conflicts_per_kernel.txt had
     // 44-47 % of this kernel's LDS cycles as bank-conflict cycles; the banking rules are per instruction (MI355X_MICROARCH.md, LDS).
     // (a) The activation tile: ds_read_b64_tr_b16 is serviced in two 32-lane halves over 64 banks; a half = two 16-lane groups
@@ -93,13 +97,15 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
     const T *xb = x + b * xsb + p0;
     const int col = lane & 31, kg = lane >> 5;
     const int mt_total = (M + 31) >> 5;
-    struct WRaw { f32x4 lo[KS], hi[KS]; float bl; };
+    struct WRaw { f32x4 lo[WIMG ? 1 : KS], hi[WIMG ? 1 : KS]; u32x4 q[WIMG ? KS : 1]; float bl; };
     auto issue = [&](int mt, WRaw &r) {   // weight fragments + the bias value of row m0 + col: one group of loads
         const int mrow = min(mt * 32 + col, M - 1);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int k0 = ks * 16 + kg * 8;
-            if constexpr (!WT) {
+            if constexpr (WIMG) {
+                r.q[ks] = wimg[((size_t)mt * KS + ks) * 64 + lane];
+            } else if constexpr (!WT) {
                 r.lo[ks] = *reinterpret_cast<const f32x4 *>(w + (size_t)mrow * K + k0);
                 r.hi[ks] = *reinterpret_cast<const f32x4 *>(w + (size_t)mrow * K + k0 + 4);
             } else {
@@ -227,7 +233,9 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
             for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const s16x8 af = m0 + col < M ? cvt8<T>(cur.lo[ks], cur.hi[ks]) : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            s16x8 af;
+            if constexpr (WIMG) af = __builtin_bit_cast(s16x8, cur.q[ks]);   // (rows past M are zeros in the image)
+            else af = m0 + col < M ? cvt8<T>(cur.lo[ks], cur.hi[ks]) : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) {
                 const T *bp = xs + ks * 16 * PX + ct * 32 + tr_off;
@@ -341,21 +349,23 @@ int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, c
 
 template <typename T, bool WT, bool LN = false>
 static int wg_launch(const T *x, const float *w, const float *bias, T *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                     const T *res, hipStream_t s, WgLnArgs<T> ln = WgLnArgs<T>{}) {
+                     const T *res, hipStream_t s, WgLnArgs<T> ln = WgLnArgs<T>{}, const void *wimg = nullptr) {
     int pt, nz;
     wg_shape(B, M, K, P, pt, nz);
     const size_t smem = wg_lds_bytes(K, pt, res != nullptr);
     dim3 grid(P / pt, B, nz);
-#define OSS_WG3(KS_, PT_, RES_)                                                                                      \
+    const u32x4 *img = reinterpret_cast<const u32x4 *>(wimg);
+#define OSS_WG3(KS_, PT_, RES_, IMG_)                                                                                \
     do {                                                                                                             \
         static LdsGate gate;                                                                                         \
-        auto kern = oss_conv1x1_wg_kernel<T, KS_, WT, PT_, RES_, (KS_ <= 6), LN>;                                        \
+        auto kern = oss_conv1x1_wg_kernel<T, KS_, WT, PT_, RES_, (KS_ <= 6), LN, IMG_>;                                  \
         if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;                         \
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, x, w, bias, y, M, P, xsb, xsk, res, ln);                      \
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, x, w, bias, y, M, P, xsb, xsk, res, ln, img);                 \
     } while (0)
 #define OSS_WG(KS_)                                                                                                  \
     do {                                                                                                             \
-        if (pt == 128) OSS_WG3(KS_, 128, false); else OSS_WG3(KS_, 64, false);                                       \
+        if (img) { if (pt == 128) OSS_WG3(KS_, 128, false, true); else OSS_WG3(KS_, 64, false, true); }              \
+        else     { if (pt == 128) OSS_WG3(KS_, 128, false, false); else OSS_WG3(KS_, 64, false, false); }            \
     } while (0)
     switch (K / 16) {
         case 1: OSS_WG(1); break;
@@ -374,14 +384,14 @@ static int wg_launch(const T *x, const float *w, const float *bias, T *y, int B,
 
 // wt = 0: y = W x + bias [+ res] with w (M, K) row-major; wt = 1: W(m, k) = w[k * M + m] (the input gradient of a (K, M) weight)
 int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-               int64_t xsk, int wt, hipStream_t s, const void *res) {
-    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res)) return OSS_ERR_SHAPE;
+               int64_t xsk, int wt, hipStream_t s, const void *res, const void *wimg) {
+    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res) || (reinterpret_cast<uintptr_t>(wimg) & 15u)) return OSS_ERR_SHAPE;
     return io_dispatch<IO_16>(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
         const T *xp = reinterpret_cast<const T *>(x), *rp = reinterpret_cast<const T *>(res);
         T *yp = reinterpret_cast<T *>(y);
-        return wt ? wg_launch<T, true>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s)
-                  : wg_launch<T, false>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s);
+        return wt ? wg_launch<T, true>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s, WgLnArgs<T>{}, wimg)
+                  : wg_launch<T, false>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s, WgLnArgs<T>{}, wimg);
     });
 }
 
@@ -491,6 +501,9 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
     }
 }
 
+// (The image form of the weight fragments (oss_conv1x1_wg_kernel's WIMG) was built for this kernel too, bit-identical, and measured no
+// gain -- 18.4 against 18.5 us at 192 -> 96, 11.7 against 11.7 at 96 -> 48, profiles/conv1x1_packed_weights_ab.txt: its one group of
+// weight loads is in flight across the copy of the dy tile either way -- so it reads the fp32 weights as before.)
 template <typename T, int KS, int PT>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_dgrad_lnbwd_kernel(const T *__restrict__ dy, const float *__restrict__ w, int M, int P, int64_t xsb, int64_t xsk,
@@ -647,12 +660,15 @@ int conv1x1_dgrad_lnbwd(oss_dtype io, const void *dy, const float *w, const void
 
 // n = LayerNorm(x) (ln_w, ln_b or NULL), mean, rstd written out; y = W n + bias.  Same shape rules as conv1x1_wg (forward only).
 int ln_conv1x1_wg(oss_dtype io, const void *x, const float *ln_w, const float *ln_b, float eps, void *n, float *mean, float *rstd,
-                  const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s) {
-    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, nullptr) || (reinterpret_cast<uintptr_t>(n) & 15u)) return OSS_ERR_SHAPE;
+                  const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s,
+                  const void *wimg) {
+    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, nullptr) || ((reinterpret_cast<uintptr_t>(n) | reinterpret_cast<uintptr_t>(wimg)) & 15u))
+        return OSS_ERR_SHAPE;
     return io_dispatch<IO_16>(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
         WgLnArgs<T> a{ln_w, ln_b, reinterpret_cast<T *>(n), mean, rstd, eps};
-        return wg_launch<T, false, true>(reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), B, M, K, P, xsb, xsk, nullptr, s, a);
+        return wg_launch<T, false, true>(reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), B, M, K, P, xsb, xsk, nullptr, s, a,
+                                         wimg);
     });
 }
 

@@ -151,7 +151,8 @@ int ln_nchw_bwd(oss_dtype xt, oss_dtype yt, const void *x, const float *w, const
 int merge4(oss_dtype io, const void *out, float *y, int B, int D, int H, int W, hipStream_t s);
 // workgroup-level 1x1 convolution (oss_conv1x1_wg.hip)
 int ln_conv1x1_wg(oss_dtype io, const void *x, const float *ln_w, const float *ln_b, float eps, void *n, float *mean, float *rstd,
-                  const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s);
+                  const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s,
+                  const void *wimg = nullptr);
 size_t conv1x1_dgrad_lnbwd_partial_floats(int B, int M, int P);
 int conv1x1_dgrad_lnbwd_ok(oss_dtype io, int M, int K, int P, int B);
 int conv1x1_dgrad_lnbwd(oss_dtype io, const void *dy, const float *w, const void *x, const float *ln_w, int with_bias, const float *mean,
@@ -162,9 +163,16 @@ void conv1x1_wg_set_pixels(int pt);
 int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, const void *x, const void *y, const float *w,
                   const void *res = nullptr);
 int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-               int64_t xsk, int wt, hipStream_t s, const void *res = nullptr);
+               int64_t xsk, int wt, hipStream_t s, const void *res = nullptr, const void *wimg = nullptr);
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res = nullptr, int f32_split = 0);
+            int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res = nullptr, int f32_split = 0,
+            const void *wimg = nullptr /* pre-packed 16-bit image of W for this direction (conv1x1_pack) */);
+// pre-packed weight images of the pixel-pair kernels (oss_conv1x1.hip)
+size_t conv1x1_image_bytes(int M, int K);
+size_t conv1x1_pack_row_bytes();
+int conv1x1_pack_rows(int cout, int cin);
+int conv1x1_pack_fill(void *rows, const float *w, void *fwd_img, void *dgrad_img, int cout, int cin);
+int conv1x1_pack(oss_dtype io, const void *table, int n_rows, hipStream_t s);
 int conv1x1_wgrad_slabs(int P);
 void conv1x1_wgrad_set_tile(int mode);
 void conv1x1_wgrad_set_span(int mult);

@@ -6,13 +6,87 @@ from __future__ import annotations
 
 import contextlib
 import os
-from typing import List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _capi, _precision
 from ._common import (_keep_operands, _recorded_before,
                       _DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_views, _planes, _ptr)  # noqa: F401
+
+
+# ---- pre-packed 16-bit weight images (csrc/oss_conv1x1.hip: oss_conv1x1_pack_kernel) ----------------------------------------
+#: storage address of a (Cout, Cin) fp32 weight -> (Cout, Cin, dtype, forward image, input-gradient image).  Set by
+#: ``GraphedTrainStep`` for the duration of ONE step, in front of which it has repacked the images from the live weights, and
+#: cleared behind it.  Deliberately no cache that outlives the step and nothing keyed on ``_version``: the fused optimizer writes
+#: the weights through raw pointers, so only the code that orders the pack launch against the optimizer can know an image is current.
+_PACKED: Dict[int, Tuple[int, int, torch.dtype, torch.Tensor, torch.Tensor]] = {}
+
+
+def set_packed_images(images: Dict[int, Tuple[int, int, torch.dtype, torch.Tensor, torch.Tensor]]) -> None:
+    """the images the following conv1x1 calls may use (``PackedConv1x1Weights.images``); replaces the previous set"""
+    _PACKED.clear()
+    _PACKED.update(images)
+
+
+def clear_packed_images() -> None:
+    _PACKED.clear()
+
+
+def packed_images_active() -> int:
+    return len(_PACKED)
+
+
+def _packed_image(w: torch.Tensor, dtype: torch.dtype, direction: int) -> int:
+    """address of the image of the contiguous fp32 (Cout, Cin) matrix ``w`` for ``direction`` (0 forward, 1 input gradient), or 0"""
+    if not _PACKED:
+        return 0
+    ent = _PACKED.get(w.data_ptr())
+    if ent is None or ent[0] != w.shape[0] or ent[1] != w.shape[1] or ent[2] != dtype or ent[3].device != w.device:
+        return 0
+    return ent[3 + direction].data_ptr()
+
+
+class PackedConv1x1Weights:
+    """Both images of a list of 1x1-convolution weights in ONE buffer, the descriptor table of the pack launch in device memory,
+    and ``refresh()`` = that launch on the current stream (capturable: the table and the buffer never move)."""
+
+    def __init__(self, weights: Sequence[torch.Tensor], dtype: torch.dtype):
+        _check(dtype in (torch.bfloat16, torch.float16), "packed weight images are 16-bit")
+        self.weights = list(weights)
+        _check(len(self.weights) > 0, "no weights to pack")
+        lib = _capi.load()
+        self.dtype, self.device = dtype, self.weights[0].device
+        shapes, off, rows = [], 0, 0
+        for w in self.weights:
+            _check(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() and w.dim() in (2, 4) and
+                   (w.dim() == 2 or (w.shape[2] == 1 and w.shape[3] == 1)), "packed weights: contiguous fp32 (Cout, Cin[, 1, 1]) on the GPU")
+            co, ci = int(w.shape[0]), int(w.shape[1])
+            fb, db = int(lib.oss_conv1x1_fwd_image_bytes(co, ci)), int(lib.oss_conv1x1_dgrad_image_bytes(co, ci))
+            shapes.append((co, ci, off, off + fb))
+            off += fb + db
+            rows += int(lib.oss_conv1x1_pack_rows(co, ci))
+        self.buffer = torch.zeros(off, dtype=torch.uint8, device=self.device)
+        _check(self.buffer.data_ptr() % 16 == 0, "image buffer must be 16-byte aligned")
+        rb = int(lib.oss_conv1x1_pack_row_bytes())
+        host = torch.zeros(rows * rb, dtype=torch.uint8)
+        self.images: Dict[int, Tuple[int, int, torch.dtype, torch.Tensor, torch.Tensor]] = {}
+        n = 0
+        for w, (co, ci, fo, do) in zip(self.weights, shapes):
+            fimg, dimg = self.buffer[fo:do], self.buffer[do:do + int(lib.oss_conv1x1_dgrad_image_bytes(co, ci))]
+            k = int(lib.oss_conv1x1_pack_fill(host.data_ptr() + n * rb, w.data_ptr(), fimg.data_ptr(), dimg.data_ptr(), co, ci))
+            _capi.check(min(k, 0), "oss_conv1x1_pack_fill")
+            n += k
+            self.images[w.data_ptr()] = (co, ci, dtype, fimg, dimg)
+        assert n == rows
+        self.n_rows = rows
+        self.table = host.to(self.device)   # set-up time: a synchronous copy, the table is read-only afterwards
+
+    def refresh(self) -> None:
+        """repack every image from the weights as they are when the launch runs"""
+        with torch.cuda.device(self.device):
+            _capi.check(_capi.load().oss_conv1x1_pack_weights(_DT[self.dtype], self.table.data_ptr(), self.n_rows,
+                                                             torch.cuda.current_stream().cuda_stream), "oss_conv1x1_pack_weights")
 
 
 def conv1x1_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
@@ -40,6 +114,12 @@ def conv1x1_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
         return y
     lib = _capi.load()
     with torch.cuda.device(x.device):
+        img = _packed_image(w, x.dtype, 0)
+        if img:
+            _capi.check(lib.oss_conv1x1_fwd_packed(_DT[x.dtype], x.data_ptr(), w.data_ptr(), img, _ptr(b), _ptr(residual), y.data_ptr(), B, Cout,
+                                                   Cin, H * W, x.stride(0), x.stride(1), torch.cuda.current_stream().cuda_stream),
+                        "oss_conv1x1_fwd_packed")
+            return y
         _capi.check(lib.oss_conv1x1_fwd(_precision.io_code(x.dtype), x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(residual), y.data_ptr(), B, Cout, Cin,
                                         H * W, x.stride(0), x.stride(1), torch.cuda.current_stream().cuda_stream), "oss_conv1x1_fwd")
     return y
@@ -73,8 +153,13 @@ def conv1x1_bwd(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, has_bia
                                               torch.cuda.current_stream().cuda_stream), "oss_conv1x1_wgrad")
             _keep(part, dw, db)
             _keep_operands(rec0, dy, x)
+        img = _packed_image(w, x.dtype, 1)
         if f32 and CONV1X1_F32_WGRAD_ONLY:
             dx = torch.nn.functional.conv_transpose2d(dy, weight.detach().float())
+        elif img:
+            _capi.check(lib.oss_conv1x1_dgrad_packed(_DT[x.dtype], dy.data_ptr(), w.data_ptr(), img, dx.data_ptr(), B, Cout, Cin, P,
+                                                     dy.stride(0), dy.stride(1), torch.cuda.current_stream().cuda_stream),
+                        "oss_conv1x1_dgrad_packed")
         else:
             _capi.check(lib.oss_conv1x1_dgrad(_precision.io_code(x.dtype), dy.data_ptr(), w.data_ptr(), dx.data_ptr(), B, Cout, Cin, P,
                                               dy.stride(0), dy.stride(1), torch.cuda.current_stream().cuda_stream), "oss_conv1x1_dgrad")
@@ -155,7 +240,8 @@ def ln_conv1x1_ok(x: torch.Tensor, weight: torch.Tensor) -> bool:
 
 def ln_conv1x1_fwd(x: torch.Tensor, ln_weight: torch.Tensor, ln_bias: Optional[torch.Tensor], weight: torch.Tensor,
                    bias: Optional[torch.Tensor]) -> List[torch.Tensor]:
-    """``n = LayerNorm_channels(x); y = F.conv2d(n, weight, bias)`` in one launch -> [y, n, mean (B, H W), rstd (B, H W)]"""
+    """``n = LayerNorm_channels(x); y = F.conv2d(n, weight, bias)`` in one launch -> [y, n, mean (B, H W), rstd (B, H W)].
+    Inside a step that has packed images (``set_packed_images``) the weight fragments come from the forward image, bit-identically."""
     B, Cin, H, W = x.shape
     Cout, P = weight.shape[0], H * W
     w = weight.detach().float().reshape(Cout, Cin).contiguous()
@@ -167,9 +253,11 @@ def ln_conv1x1_fwd(x: torch.Tensor, ln_weight: torch.Tensor, ln_bias: Optional[t
     mean = torch.empty((B, P), dtype=torch.float32, device=x.device)
     rstd = torch.empty((B, P), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _capi.check(_capi.load().oss_ln_conv1x1_fwd(_DT[x.dtype], x.data_ptr(), lw.data_ptr(), _ptr(lb), 1e-5, n.data_ptr(), mean.data_ptr(),
-                                                    rstd.data_ptr(), w.data_ptr(), _ptr(b), y.data_ptr(), B, Cout, Cin, P, x.stride(0),
-                                                    x.stride(1), torch.cuda.current_stream().cuda_stream), "oss_ln_conv1x1_fwd")
+        # (image 0 = none: the call is then oss_ln_conv1x1_fwd itself)
+        _capi.check(_capi.load().oss_ln_conv1x1_fwd_packed(_DT[x.dtype], x.data_ptr(), lw.data_ptr(), _ptr(lb), 1e-5, n.data_ptr(),
+                                                           mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), _packed_image(w, x.dtype, 0) or None,
+                                                           _ptr(b), y.data_ptr(), B, Cout, Cin, P, x.stride(0), x.stride(1),
+                                                           torch.cuda.current_stream().cuda_stream), "oss_ln_conv1x1_fwd")
     return [y, n, mean, rstd]
 
 

@@ -55,12 +55,15 @@ class GraphedTrainStep:
                  fused_optimizer: bool = True, split_graphs: bool = False, overlap_wgrads: bool = False,
                  defer_finishes: bool = True, micro_streams: int = 1, weight_decay: float = 0.0,
                  clip_grad_norm: Optional[float] = None, multi_shape: bool = False, grad_buckets: int = 1,
-                 allreduce_via_host: bool = False):
+                 allreduce_via_host: bool = False, packed_weights: bool = True):
         """``weight_decay`` / ``clip_grad_norm`` / ``ema_decay=0``: the Deraining step (AdamW + clip_grad_norm_(0.01), no
         EMA: Deraining/basicsr/models/image_restoration_model.py:121-167).  ``multi_shape``: keep one forward+backward
         graph per (lq, gt) shape -- the progressive patch schedule of that tree changes the patch size and the batch
         six times (Deraining/basicsr/train.py:213-271) -- all sharing ONE optimizer graph (implies ``split_graphs``: the
-        gradients then always sit in the same flat buffer, so the optimizer's pointer table never changes)."""
+        gradients then always sit in the same flat buffer, so the optimizer's pointer table never changes).
+        ``packed_weights``: the MFMA 1x1 convolutions that read the fp32 masters (the layers kept out of the shadows below) get
+        their weight fragments from 16-bit images in MFMA order that ONE launch at the head of every step repacks from the live
+        masters (ops/pointwise.py ``PackedConv1x1Weights``); bit-identical to ``False``, which is there for A-B timing."""
         self.net = net
         self.params = [p for p in net.parameters() if p.requires_grad]
         self.device = self.params[0].device
@@ -84,6 +87,7 @@ class GraphedTrainStep:
         # 16-bit shadows of the parameters autocast would cast per use (conv weights / biases and the
         # projection matrices of SS2D_1); norms, A_logs, D, dt biases and the fp32 channel branch stay fp32
         self.shadow = {}
+        packable = []   # weights of the MFMA 1x1 layers that stay fp32 masters: candidates for the packed images
         if shadow_weights and autocast_dtype is not None:
             mods = dict(net.named_modules())
             for name, p in net.named_parameters():
@@ -94,7 +98,9 @@ class GraphedTrainStep:
                 dense_conv = isinstance(m, torch.nn.Conv2d) and m.groups == 1  # depth-wise convs run on our fp32-weight kernel
                 if dense_conv and m.kernel_size == (1, 1) and _ops.pointwise.CONV1X1_IMPL == "mfma" and owner.rsplit(".", 1)[-1] in (
                         "in_conv", "out_conv", "project_in", "project_out", "reduce_chan_level2", "reduce_chan_level3"):
-                    continue  # the MFMA 1x1 kernels read the fp32 masters and narrow them in their loader
+                    if leaf == "weight":
+                        packable.append(p)
+                    continue  # the MFMA 1x1 kernels read the fp32 masters (narrowed in their loader, or pre-packed: below)
                 if dense_conv and m.kernel_size == (3, 3) and min(m.in_channels, m.out_channels) <= 4 and _ops.conv3x3.THIN_IMPL:
                     continue  # patch_embed / the tail's last layer: the thin-convolution kernels read the fp32 masters (ops/conv3x3.py)
                 if dense_conv and m.kernel_size == (3, 3) and _ops.conv3x3.DENSE_IMPL and m.in_channels % 16 == 0 and m.out_channels >= 5 \
@@ -104,6 +110,12 @@ class GraphedTrainStep:
                 fused_proj = getattr(m, "fused_core", False) and getattr(m, "omni", False)
                 if dense_conv or (leaf in ("x_proj_weight", "dt_projs_weight") and not fused_proj):
                     self.shadow[name] = (p, torch.empty_like(p, dtype=autocast_dtype).requires_grad_())
+        # a container of its own (``shadow`` keeps meaning "runs on a 16-bit leaf"): both images of every such weight + the table
+        self.packed = None
+        if packed_weights and autocast_dtype in (torch.bfloat16, torch.float16):
+            packable = [p for p in packable if p.dtype == torch.float32 and p.is_contiguous()]
+            if packable:
+                self.packed = _ops.pointwise.PackedConv1x1Weights(packable, autocast_dtype)
         self._masters = [m for m, _ in self.shadow.values()]
         self._shadows = [s for _, s in self.shadow.values()]
         self._master_grads = [torch.zeros_like(m) for m in self._masters]
@@ -325,8 +337,18 @@ class GraphedTrainStep:
             _ops.flush_finishes(self.ftables[slot])
 
     def _fwd_bwd(self):
-        if self.nmicro > 1:
-            return self._fwd_bwd_micro()
+        """one step's forward + backward.  The packed weight images are refreshed ONCE at its head (a captured launch: every
+        replay repacks from the masters the optimizer just wrote) and are visible to the 1x1 ops only until it returns."""
+        if self.packed is None:
+            return self._fwd_bwd_micro() if self.nmicro > 1 else self._fwd_bwd_single()
+        self.packed.refresh()   # on the current stream, in front of the fork of the micro-batch branches
+        _ops.pointwise.set_packed_images(self.packed.images)
+        try:
+            return self._fwd_bwd_micro() if self.nmicro > 1 else self._fwd_bwd_single()
+        finally:
+            _ops.pointwise.clear_packed_images()
+
+    def _fwd_bwd_single(self):
         for p in self.params:  # host-side only: the backward then assigns instead of accumulating
             p.grad = None
         for s_ in self._shadows:
