@@ -475,8 +475,6 @@ typedef struct {
     const float *Dsc;               /* (2 dc)                                                                */
     const float *cout_w, *cout_b;   /* conv_cout (dc) weight / (1) bias, or NULL                             */
     const float *cn_w, *cn_b;       /* channel_norm weight / bias (L)                                        */
-    float *zt;                      /* (B, 2, L, Cc)   saved: projections, c fastest                         */
-    float *dts;                     /* (B, 2 dc, L)    saved: dt_proj output before bias / softplus          */
     float *hs;                      /* (B, 2 dc, L, 16) saved: the scan state after every step               */
     float *y;                       /* (B, 2 dc, L)    saved: scan outputs (direction 1 stored un-flipped)   */
     float *yc;                      /* (B, L)          saved: LayerNorm input                                */
@@ -804,12 +802,13 @@ int oss_f32_matmul_modes(void);
 /* ABI guard.  oss_scan_fwd_params / oss_scan_bwd_params / oss_chan_params cross the boundary BY POINTER, so a binding layer
  * compiled against another revision of this header would hand the kernels garbage pointers.  OSS_ABI_VERSION is bumped with
  * every change of a struct or of an entry point's argument list (9: the pre-packed weight images of the 1x1 convolutions,
- * oss_conv1x1_pack_* and the *_packed entry points; no struct changed); oss_abi_struct_bytes(which) is the library's own sizeof
+ * oss_conv1x1_pack_* and the *_packed entry points; 10: oss_chan_params lost zt and dts, the channel kernels evaluate the
+ * projections from the pooled vector); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 9
+#define OSS_ABI_VERSION 10
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

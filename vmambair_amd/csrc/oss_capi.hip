@@ -674,7 +674,8 @@ int oss_cross_merge2(oss_dtype io, const void *g2, void *dx, int batch, int D, i
 }
 
 int oss_chan_fwd(const oss_chan_params *p, oss_stream_t stream) {
-    fam_count(FAM_CHAN, p ? 4.0 * p->B * ((double)p->L * (2.0 * p->Cc + 2.0 * p->dc * 18.0 + 3.0) + (p->pool_part ? (double)p->n_part * p->L : p->L)) : 0.0);
+    // hs (16 floats per row and step) and y saved, pooled / yc / c; the projections are never written
+    fam_count(FAM_CHAN, p ? 4.0 * p->B * ((double)p->L * (2.0 * p->dc * 17.0 + 3.0) + (p->pool_part ? (double)p->n_part * p->L : p->L)) : 0.0);
     if (!p) return OSS_ERR_NULL;
     return chan_fwd(*p, reinterpret_cast<hipStream_t>(stream));
 }
@@ -683,7 +684,7 @@ size_t oss_chan_grad_floats(int L, int dc, int Rc, int Cc) { return chan_grad_fl
 size_t oss_chan_bwd_scratch_floats(int B, int L, int dc, int Rc, int Cc) { return chan_bwd_scratch_floats(B, L, dc, Rc, Cc); }
 
 int oss_chan_bwd(const oss_chan_params *p, const float *gc, float *dpooled, float *grads, float *scratch, oss_stream_t stream) {
-    fam_count(FAM_CHAN, p ? 4.0 * p->B * ((double)p->L * (2.0 * p->Cc + 2.0 * p->dc * 18.0 + 5.0)) : 0.0);
+    fam_count(FAM_CHAN, p ? 4.0 * p->B * ((double)p->L * (2.0 * p->dc * 17.0 + 5.0)) : 0.0);
     if (!p) return OSS_ERR_NULL;
     return chan_bwd(*p, gc, dpooled, grads, scratch, reinterpret_cast<hipStream_t>(stream));
 }

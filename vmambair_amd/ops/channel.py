@@ -15,20 +15,23 @@ from ._common import (_DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_vi
 
 def chan_supported(dc: int, n_state: int, d_inner: int) -> bool:
     """shapes oss_channel.hip covers: dc_state 16, dc_inner <= 4, the rows of one image LDS-resident in both kernels (every
-    reference config: d_inner <= 384; the backward's resident set -- sequences, gradients, the four state groups' partial sums --
-    is the larger one: (18 dc + 1) d_inner + 2 dc (dc + 32) + 8 floats of the CU's 160 KiB)"""
-    lds_bwd = 4 * ((18 * dc + 1) * d_inner + 2 * dc * (dc + 32 + 8) + 8)
-    return n_state == 16 and 1 <= dc <= 4 and lds_bwd <= 160 * 1024
+    reference config: d_inner <= 384; the forward's resident set -- the pooled vector, y, yc and the four state groups' partial
+    sums of y, next to the coefficient table -- is the larger one: (10 dc + 2) d_inner + 4 (rank + 32) + 6 dc + 8 floats of the
+    CU's 160 KiB, with the channel dt rank of the reference configs, 6 or ceil(d_inner / 16); the backward keeps 9 d_inner and a
+    few hundred)"""
+    rank = max(6, -(-d_inner // 16))
+    lds_fwd = 4 * ((10 * dc + 2) * d_inner + 4 * (rank + 32) + 6 * dc + 8)
+    return n_state == 16 and 1 <= dc <= 4 and lds_fwd <= 160 * 1024
 
 
 def _chan_params(B, L, pooled, prm, saved, c):
     cin_w, cin_b, Wxc, Wdtc, dt_bias, A_logs, Dsc, cout_w, cout_b, cn_w, cn_b = prm
-    zt, dts, hs, y, yc, stat = saved
+    hs, y, yc, stat = saved
     P = _capi.ChanParams()
     P.B, P.L, P.dc, P.Rc, P.Cc = B, L, Wdtc.shape[1], Wdtc.shape[2], Wxc.shape[1]
     for name, t in (("pooled", pooled), ("cin_w", cin_w), ("cin_b", cin_b), ("Wxc", Wxc), ("Wdtc", Wdtc), ("dt_bias", dt_bias),
                     ("A_logs", A_logs), ("Dsc", Dsc), ("cout_w", cout_w), ("cout_b", cout_b), ("cn_w", cn_w), ("cn_b", cn_b),
-                    ("zt", zt), ("dts", dts), ("hs", hs), ("y", y), ("yc", yc), ("stat", stat), ("c", c)):
+                    ("hs", hs), ("y", y), ("yc", yc), ("stat", stat), ("c", c)):
         setattr(P, name, _ptr(t))
     P.pool_part, P.n_part, P.pool_scale = None, 0, 0.0
     return P
@@ -39,7 +42,8 @@ def chan_gate_fwd(y2: torch.Tensor, cin_w: Optional[torch.Tensor], cin_b: Option
                   cout_w: Optional[torch.Tensor], cout_b: Optional[torch.Tensor], cn_w: torch.Tensor, cn_b: torch.Tensor,
                   mul_mode: bool, pool_part: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """``y2 * c + y2`` (mul_mode) or ``y2 + c`` with c = the channel branch of SS2D_1 evaluated on mean_hw(y2)
-    (MambaSISR6_arch.py:438-496) -> [out, c, pooled, zt, dts, hs, y, yc, stat] (all but ``out`` are saved for bwd).
+    (MambaSISR6_arch.py:438-496) -> [out, c, pooled, zt, dts, hs, y, yc, stat] (all but ``out`` are saved for bwd; ``zt`` and
+    ``dts`` are empty: the kernels evaluate the projections from ``pooled`` and never store them).
     ``pool_part`` (B, tiles, d) fp32: the per-workgroup sums of y2 its producer left (``ln_nchw_fwd(want_pool=True)``): the pooling
     pass over y2 is skipped and ``pooled`` is formed inside the channel kernel."""
     _check(y2.is_cuda and y2.dim() == 4 and y2.dtype in _DT, "chan_gate: y2 must be a (B, d, H, W) GPU tensor")
@@ -52,11 +56,12 @@ def chan_gate_fwd(y2: torch.Tensor, cin_w: Optional[torch.Tensor], cin_b: Option
     dev = y2.device
     f = dict(dtype=torch.float32, device=dev)
     pooled, c = torch.empty((B, d), **f), torch.empty((B, d), **f)
-    saved = (torch.empty((B, 2, d, Cc), **f), torch.empty((B, 2 * dc, d), **f), torch.empty((B, 2 * dc, d, 16), **f),
-             torch.empty((B, 2 * dc, d), **f), torch.empty((B, d), **f), torch.empty((B, 2), **f))
+    unused = (torch.empty((0,), **f), torch.empty((0,), **f))   # the slots of zt and dts in the op's result list
+    saved = (torch.empty((B, 2 * dc, d, 16), **f), torch.empty((B, 2 * dc, d), **f), torch.empty((B, d), **f),
+             torch.empty((B, 2), **f))
     out = torch.empty((B, d, H, W), dtype=y2.dtype, device=dev)
     if y2.numel() == 0:
-        return [out, c, pooled, *saved]
+        return [out, c, pooled, *unused, *saved]
     lib = _capi.load()
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
@@ -72,7 +77,7 @@ def chan_gate_fwd(y2: torch.Tensor, cin_w: Optional[torch.Tensor], cin_b: Option
         _capi.check(lib.oss_row_affine(_DT[y2.dtype], y2.data_ptr(), c.data_ptr() if mul_mode else None,
                                        None if mul_mode else c.data_ptr(), out.data_ptr(), B, d, H * W, y2.stride(0),
                                        y2.stride(1), 1.0, st), "oss_row_affine")
-    return [out, c, pooled, *saved]
+    return [out, c, pooled, *unused, *saved]
 
 
 def chan_gate_bwd(g: torch.Tensor, y2: torch.Tensor, c: torch.Tensor, pooled: torch.Tensor, zt: torch.Tensor, dts: torch.Tensor,
@@ -100,7 +105,7 @@ def chan_gate_bwd(g: torch.Tensor, y2: torch.Tensor, c: torch.Tensor, pooled: to
         # gradient of c: sum over the pixels of g * y2 (mul_add) or of g (add)
         _capi.check(lib.oss_rowsum(_DT[y2.dtype], g.data_ptr(), y2.data_ptr() if mul_mode else None, gc.data_ptr(), B, d, H * W,
                                    g.stride(0), g.stride(1), y2.stride(0), y2.stride(1), 1.0, st), "oss_rowsum")
-        _capi.check(lib.oss_chan_bwd(_chan_params(B, d, pooled, prm, (zt, dts, hs, y, yc, stat), c), gc.data_ptr(),
+        _capi.check(lib.oss_chan_bwd(_chan_params(B, d, pooled, prm, (hs, y, yc, stat), c), gc.data_ptr(),
                                      dpool.data_ptr(), grads.data_ptr(), scratch.data_ptr(), st), "oss_chan_bwd")
         _keep(scratch, grads)
         if fold:
