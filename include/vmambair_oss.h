@@ -741,6 +741,52 @@ int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, d
                       int64_t b_batch_stride, int64_t b_channel_stride, int64_t b_row_stride, int crop_border, int flags,
                       oss_stream_t stream);
 
+/* The reference's pixel losses with their gradients on the device (oss_pixel_loss.hip): L1Loss, MSELoss, PSNRLoss (with toY) and
+ * CharbonnierLoss of Deraining/basicsr/models/losses/losses.py:26-122 with the weighting and reduction of weight_reduce_loss
+ * (losses/loss_util.py:25-54).  lw = loss_weight, d = pred - target, n = batch * channels * plane:
+ *   OSS_LOSS_L1, OSS_LOSS_MSE   lw * sum(term) / n with term = |d| or d^2; OSS_LOSS_SUM: lw * sum(term).  With a weight
+ *                               (OSS_LOSS_WEIGHT: (batch, channels, H, W); OSS_LOSS_WEIGHT_1CH: (batch, 1, H, W), broadcast over the
+ *                               channels by the kernel) term * w, and the mean divides by sum(w), resp. channels * sum(w)
+ *                               (loss_util.py:47-52).  d|d| / dd = sign(d) with sign(0) = 0, as torch
+ *   OSS_LOSS_CHARBONNIER        sum(sqrt(d^2 + eps^2)) / n; loss_weight is accepted and unused, as in the reference (losses.py:114-122)
+ *   OSS_LOSS_PSNR               lw * (10 / ln 10) * mean_b ln(mse_b + 1e-8), mse_b = the mean of d^2 over image b (losses.py:109);
+ *                               OSS_LOSS_TOY (channels == 3): on y = (k0 R + k1 G + k2 B + 16) / 255 with k = the fp32 values of
+ *                               65.481, 128.553, 24.966 (losses.py:92, :102-105) -- dy is formed from the three differences, the
+ *                               + 16 cancels -- and mse_b over the H W pixels
+ *   pred      (batch, channels, H, W) dense, fp32 / fp16 / bf16 (pred_io); plane = H * W
+ *   target    the same shape, dense, fp32 or pred's type (target_io)
+ *   weight    fp32, dense, NULL unless one of the two weight flags is set (L1 and MSE only)
+ *   loss      one fp32 scalar in device memory, rounded once from the fp64 result
+ *   stats     oss_pixel_loss_stat_doubles(...) doubles the forward writes and the backward reads: the denominator of the mean
+ *             (1 for OSS_LOSS_SUM), or for PSNR mse_b per image
+ *   partials  oss_pixel_loss_partial_doubles(...) doubles of scratch, no init
+ * Arithmetic order: every element is widened to fp32, d and the term (and term * w) are fp32, every sum is fp64.  A workgroup owns
+ * 2048 consecutive elements (for PSNR: of one image) and writes one fp64 partial (two with a weight: sum term * w, sum w) after a
+ * fixed reduction; a second, single-workgroup launch of the same call adds the partials in a fixed order.  No atomics: reruns are
+ * bit-identical, no host read-back, capturable into a hipGraph.  oss_pixel_loss_bwd is one launch: dpred (pred's type) =
+ * grad_output (one fp32 scalar in device memory) * d loss / d pred, each value formed in fp32 and rounded once.
+ * oss_pixel_loss_partial_doubles is a pure host query and the support query: 0 when the combination is not taken -- pred_io or
+ * target_io no element type, a 16-bit target that is not pred's type, an unknown kind or flag, a weight or OSS_LOSS_SUM with
+ * Charbonnier / PSNR, both weight flags, OSS_LOSS_TOY without PSNR or with channels != 3, a dimension < 1 or more than 2^31 - 1
+ * workgroups.  The entry points return OSS_ERR_SHAPE for the same, OSS_ERR_NULL for a missing pointer. */
+#define OSS_LOSS_L1 0
+#define OSS_LOSS_MSE 1
+#define OSS_LOSS_CHARBONNIER 2
+#define OSS_LOSS_PSNR 3
+#define OSS_LOSS_SUM 1
+#define OSS_LOSS_TOY 2
+#define OSS_LOSS_WEIGHT 4
+#define OSS_LOSS_WEIGHT_1CH 8
+size_t oss_pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t batch, int64_t channels,
+                                      int64_t plane);
+size_t oss_pixel_loss_stat_doubles(int kind, int flags, int64_t batch, int64_t channels, int64_t plane);
+int oss_pixel_loss_fwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, const void *pred, const void *target,
+                       const float *weight, float *loss, double *stats, double *partials, int64_t batch, int64_t channels,
+                       int64_t plane, float loss_weight, float eps, oss_stream_t stream);
+int oss_pixel_loss_bwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, const void *pred, const void *target,
+                       const float *weight, const double *stats, const float *grad_output, void *dpred, int64_t batch,
+                       int64_t channels, int64_t plane, float loss_weight, float eps, oss_stream_t stream);
+
 /* Training batches cut on the device (oss_pairs.hip): a pool of decoded image pairs resident in device memory, a counter-based draw
  * and one gather launch per batch -- paired_random_crop, augment / random_augmentation (Deraining/basicsr/data/transforms.py:24-83,
  * :136-200, :223-275), img2tensor(bgr2rgb, float32) of img / 255. (utils/img_util.py:9-40) and EnlargedSampler's rank-strided epoch

@@ -805,6 +805,31 @@ int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, d
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t oss_pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t batch, int64_t channels,
+                                      int64_t plane) {
+    return pixel_loss_partial_doubles(kind, flags, pred_io, target_io, batch, channels, plane);
+}
+size_t oss_pixel_loss_stat_doubles(int kind, int flags, int64_t batch, int64_t channels, int64_t plane) {
+    return pixel_loss_stat_doubles(kind, flags, batch, channels, plane);
+}
+static bool pixel_loss_weight_ok(int flags, const float *weight) {
+    return ((flags & (OSS_LOSS_WEIGHT | OSS_LOSS_WEIGHT_1CH)) != 0) == (weight != nullptr);
+}
+int oss_pixel_loss_fwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, const void *pred, const void *target,
+                       const float *weight, float *loss, double *stats, double *partials, int64_t batch, int64_t channels,
+                       int64_t plane, float loss_weight, float eps, oss_stream_t stream) {
+    if (!pred || !target || !loss || !stats || !partials || !pixel_loss_weight_ok(flags, weight)) return OSS_ERR_NULL;
+    return pixel_loss_fwd(kind, flags, pred_io, target_io, pred, target, weight, loss, stats, partials, batch, channels, plane,
+                          loss_weight, eps, reinterpret_cast<hipStream_t>(stream));
+}
+int oss_pixel_loss_bwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, const void *pred, const void *target,
+                       const float *weight, const double *stats, const float *grad_output, void *dpred, int64_t batch,
+                       int64_t channels, int64_t plane, float loss_weight, float eps, oss_stream_t stream) {
+    if (!pred || !target || !stats || !grad_output || !dpred || !pixel_loss_weight_ok(flags, weight)) return OSS_ERR_NULL;
+    return pixel_loss_bwd(kind, flags, pred_io, target_io, pred, target, weight, stats, grad_output, dpred, batch, channels, plane,
+                          loss_weight, eps, reinterpret_cast<hipStream_t>(stream));
+}
+
 void oss_set_defer_wgrad(int on) {
     std::lock_guard<std::mutex> lk(g_defer_mu);
     g_defer_wgrad.store(on ? 1 : 0);

@@ -10,6 +10,7 @@ One module per operator family (round 1 had a single 1 000-line ``ops.py``):
                 for the GEMM-shaped ones of the skeleton (Downsample, Upsample, the x4 tail)
   ``dwconv``    depth-wise 3x3 (+ silu)          ``layernorm``  NCHW LayerNorm (+ gate)          ``ffn``  gelu gate of the EFFN
   ``metrics``   validation PSNR + SSIM of a batch of image pairs in one call (mean squared error, mean SSIM; fp64 on the device)
+  ``losses``    the pixel losses (L1, MSE, Charbonnier, PSNR) with their gradient w.r.t. the prediction: fp64 sums in a fixed order
   ``pairs``     training batches cut from a device-resident pool of image pairs: counter-based draw + one crop / flip / convert launch
   ``_common``   dtype table, checks, deferred finishing, weight-gradient side stream
 Everything is re-exported here, so ``from vmambair_amd import ops; ops.selective_scan_fwd(...)`` keeps working.  Module-level
@@ -19,7 +20,7 @@ No CPU implementation exists: CPU tensors are rejected exactly as the reference 
 cus/selective_scan.cpp:174).
 """
 from .. import _capi  # noqa: F401
-from . import _common, channel, conv3x3, core, dwconv, ffn, layernorm, metrics, pairs, pointwise, scan  # noqa: F401
+from . import _common, channel, conv3x3, core, dwconv, ffn, layernorm, losses, metrics, pairs, pointwise, scan  # noqa: F401
 from ._common import (WGRAD_STATS, WgradTable, flush_wgrads, pending_wgrad_table_bytes, pending_wgrads, _keep_operands,  # noqa: F401
                       FinishTable, _DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_views, _planes, _ptr,  # noqa: F401
                       deferred_finishes, flush_finishes, orphaned_deferred_outputs, pending_finish_chunks, scan_chunk,
@@ -36,6 +37,7 @@ from .conv3x3 import DenseConv3x3Fn, conv3x3_dense_bwd, conv3x3_dense_fwd, dense
 from .conv3x3 import conv3x3 as conv3x3_layer  # noqa: F401
 from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gate, gelu_gate_bwd, gelu_gate_fwd  # noqa: F401
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401
+from .losses import pixel_loss_bwd, pixel_loss_fwd, pixel_loss_ok  # noqa: F401
 from .metrics import image_metrics, image_metrics_ok  # noqa: F401
 from .pairs import pairs_draw, pairs_gather, pairs_ok  # noqa: F401
 from .scan import merge4, selective_scan_bwd, selective_scan_fwd  # noqa: F401

@@ -361,7 +361,10 @@ class GraphedTrainStep:
                 out = torch.func.functional_call(self.net, self._shadow_map, (self.static_lq,))
             else:
                 out = self.net(self.static_lq)
-        loss = self.loss_fn(out.float(), self.static_gt)
+        if getattr(self.loss_fn, "takes_network_dtype", False):   # vmambair_amd.losses: widened inside the loss kernels
+            loss = self.loss_fn(out, self.static_gt)
+        else:
+            loss = self.loss_fn(out.float(), self.static_gt)
         self._backward(loss, list(self.params) + self._shadows)
         if self.nbuckets > 1:
             return loss.detach()   # gradients are finished, converted and packed bucket by bucket (_flush_bucket)
@@ -395,7 +398,10 @@ class GraphedTrainStep:
                 lq, gt = self.static_lq[m * mb:(m + 1) * mb], self.static_gt[m * mb:(m + 1) * mb]
                 with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
                     out = torch.func.functional_call(self.net, leaves, (lq,))
-                loss = self.loss_fn(out.float(), gt) / M     # mean over the whole batch = mean of the micro-batch means
+                if getattr(self.loss_fn, "takes_network_dtype", False):
+                    loss = self.loss_fn(out, gt) / M
+                else:
+                    loss = self.loss_fn(out.float(), gt) / M     # mean over the whole batch = mean of the micro-batch means
                 self._backward(loss, list(leaves.values()), m)
                 losses.append(loss.detach())
         for st in self.mstreams:
