@@ -811,7 +811,23 @@ int oss_pixel_loss_bwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_
  * written as 0 and *clamped (an int in device memory the caller zeroed) is set to 1.
  * oss_pairs_ok is a pure host query: channels 1 or 3, 1 <= scale <= 64, 1 <= patch sides, scale * side <= 2^20, 1 <= batch <= 65535
  * and at most 65535 tiles of 32 x 32 pixels per sample (LQ + GT).  oss_pairs_philox evaluates one Philox4x32-10 block (4 counter
- * words, 2 key words -> 4 words) on the HOST from the text the kernels are compiled from. */
+ * words, 2 key words -> 4 words) on the HOST from the text the kernels are compiled from.
+ *
+ * The Deraining tree's loader pads and its training loop cuts a second window (paired_image_dataset.py:101-113, utils/img_util.py:
+ * 148-164, train.py:213-271); two sibling entry points do both in the same two launches, the two above are unchanged:
+ * oss_pairs_draw_window: the two-stage draw.  Every image counts as extended to max(side, pad_to) (pad_to = 0: as it is); top and
+ * left of a crop of side full_patch >= patch come from the words oss_pairs_draw uses, with range max(lq_h, pad_to) - full_patch + 1
+ * (and lq_w likewise); ONE window per call comes from words 0, 1 of the Philox block with counter (g0 lo, g0 hi, 0x77696e64, 0), g0 =
+ * c * world + rank the global position of the call's first sample: x0 = (word 0 * (full_patch - patch)) >> 32 (rows of the augmented
+ * crop), y0 likewise (columns) -- the support {0 .. full_patch - patch - 1} of int((G - m) * random()), {0} when equal.  The sample
+ * stored is the crop's window as one ordinary sample of side patch: with (wr, wc) = transpose ? (y0, x0) : (x0, y0), top + (vflip ?
+ * full_patch - patch - wr : wr), left + (hflip ? full_patch - patch - wc : wc), and the same code.  All sizes in LQ pixels.  With
+ * full_patch == patch and pad_to == 0 the samples are those of oss_pairs_draw, bit for bit; the counter is handled the same way.
+ * oss_pairs_gather_padded: oss_pairs_gather on images extended at the bottom and right to max(side, pad_to) by cv2.BORDER_REFLECT
+ * (fedcba|abcdefgh|hgfedcb): row or column i >= n of an image with n rows / columns is read at r = i mod 2n, r < n ? r : 2n - 1 - r
+ * (periodic: an image smaller than pad_to / 2 is covered).  Nothing is stored and nothing outside the image's own bytes is read; a
+ * rectangle that does not fit even the extended image is clamped, zero-filled and flagged as above.  The reference pads LQ and GT by
+ * the same pixel count, which is a pair only at scale 1: pad_to > 0 needs scale == 1 (OSS_ERR_SHAPE otherwise); 0 <= pad_to <= 2^20. */
 #define OSS_PAIRS_HFLIP 1
 #define OSS_PAIRS_ROT 2
 int oss_pairs_philox(const uint32_t *counter, const uint32_t *key, uint32_t *out);
@@ -820,6 +836,11 @@ int oss_pairs_draw(const int64_t *table, int n_pairs, int64_t *counter, int *sam
                    int world, int flags, oss_stream_t stream);
 int oss_pairs_gather(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq, float *gt,
                      int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb, oss_stream_t stream);
+int oss_pairs_draw_window(const int64_t *table, int n_pairs, int64_t *counter, int *samples, int batch, int patch, int full_patch,
+                          int pad_to, int64_t seed, int rank, int world, int flags, oss_stream_t stream);
+int oss_pairs_gather_padded(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq,
+                            float *gt, int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb,
+                            int pad_to, oss_stream_t stream);
 
 /* Algorithmic bytes of the block's NON-scan launches, by kernel family (round 6; bench.py `roofline.non_scan`).  While counting
  * is on, every entry point of this header that launches a kernel adds the bytes its launch must move at minimum (each operand

@@ -36,8 +36,26 @@
 // A rectangle that does not fit its image (or a pair index / offset outside the pool) is clamped, what cannot be read is written
 // as 0 and *clamped is set to 1 (a plain store of the same value from whoever sees it): a defence, the host layer validates.
 //
+//
+// The Deraining tree's loader (paired_image_dataset.py:101-113, train.py:213-271) does two more things, both folded into the same
+// two launches by a sibling of the draw and a second instantiation of the gather; the plain forms keep their device code:
+//   padding              utils/img_util.py:148-164: both images extended at the bottom and right to gt_size by cv2.BORDER_REFLECT
+//                        (fedcba|abcdefgh|hgfedcb): index i >= n reads r = i mod 2n, r < n ? r : 2n - 1 - r -- periodic, so an image
+//                        below gt_size / 2 is covered.  Nothing is stored: oss_pairs_gather_kernel<C, PairPadArgs> reads rows and columns
+//                        at or beyond the image through that map.  A tile row's in-image columns keep the aligned-word path; the
+//                        reflected columns run backwards in memory and are byte loads, one pixel per thread.
+//   progressive window   every iteration cuts ONE window [x0 : x0 + m, y0 : y0 + m] (x0 rows, y0 columns), common to the batch, out of
+//                        the augmented gt_size patches.  With (wr, wc) = transpose ? (y0, x0) : (x0, y0) that is the ordinary sample
+//                        of side m at (top + (vflip ? G - m - wr : wr), left + (hflip ? G - m - wc : wc)) with the same code, which is
+//                        what oss_pairs_draw_window_kernel emits: the gather never reads the large patch to produce the small one.
+//                        x0, y0 = words 0, 1 of one more Philox block per call, counter (g0 lo, g0 hi, "wind", 0), g0 the global
+//                        position of the call's first sample; (uint64(r) * (G - m)) >> 32 never yields G - m, as int((G - m) *
+//                        random()) never does.
+//
 // hipcc -Rpass-analysis=kernel-resource-usage, gfx950: see DESIGN.md 4.4d.  Timings: profiles/pairs_kernel_timing.txt.
 #include "oss_host.h"
+
+#include <type_traits>
 
 namespace oss {
 
@@ -55,6 +73,7 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 
 constexpr uint32_t kTagPerm = 0x7065726du, kTagCrop = 0x63726f70u;   // "perm", "crop": word 3 / word 2 of the two counter forms
+constexpr uint32_t kTagWind = 0x77696e64u;                           // "wind": word 2 of the per-call window block
 
 // keyed bijection of [0, n): 4 Feistel rounds on 2 * half bits (4^half >= n), walked until the value is back inside [0, n)
 __host__ __device__ inline uint32_t pairs_perm(uint32_t x, uint32_t n, uint64_t epoch, uint32_t k0, uint32_t k1) {
@@ -93,6 +112,35 @@ oss_pairs_draw_kernel(const int64_t *__restrict__ table, int n, int64_t *counter
     }
 }
 
+// the two-stage draw: a crop of side `full` from the image padded to `pad`, then the call's common window of side `patch` inside the
+// augmented crop, emitted as one sample of side `patch`.  full == patch and pad == 0: the samples of oss_pairs_draw_kernel
+__global__ void __launch_bounds__(256)
+oss_pairs_draw_window_kernel(const int64_t *__restrict__ table, int n, int64_t *counter, int *__restrict__ samples, int batch, int patch,
+                             int full, int pad, uint32_t k0, uint32_t k1, int rank, int world, int code_mask) {
+    const uint64_t c = (uint64_t)*counter;
+    __syncthreads();                                   // every thread has read c ...
+    if (threadIdx.x == 0) *counter = (int64_t)(c + (uint64_t)batch);   // ... before it moves
+    const uint64_t g0 = c * (uint64_t)world + (uint64_t)rank;
+    const Philox4 win = philox4x32_10((uint32_t)g0, (uint32_t)(g0 >> 32), kTagWind, 0u, k0, k1);
+    const uint32_t span = (uint32_t)(full - patch);
+    const int wx0 = (int)(((uint64_t)win.v[0] * span) >> 32), wy0 = (int)(((uint64_t)win.v[1] * span) >> 32);   // rows, columns
+    for (int b = threadIdx.x; b < batch; b += 256) {
+        const uint64_t g = (c + (uint64_t)b) * (uint64_t)world + (uint64_t)rank;
+        const uint64_t epoch = g / (uint64_t)n;
+        const uint32_t pair = pairs_perm((uint32_t)(g - epoch * (uint64_t)n), (uint32_t)n, epoch, k0, k1);
+        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), kTagCrop, 0u, k0, k1);
+        const int64_t mh = max(table[4 * (int64_t)pair + 2], (int64_t)pad) - full + 1;
+        const int64_t mw = max(table[4 * (int64_t)pair + 3], (int64_t)pad) - full + 1;
+        const uint32_t uh = mh < 1 ? 1u : (uint32_t)mh, uw = mw < 1 ? 1u : (uint32_t)mw;   // a too-small image: the gather clamps and flags
+        const int code = (int)(r.v[2] >> 29) & code_mask;
+        const int wr = (code & 4) ? wy0 : wx0, wc = (code & 4) ? wx0 : wy0;
+        samples[4 * b + 0] = (int)pair;
+        samples[4 * b + 1] = (int)(((uint64_t)r.v[0] * uh) >> 32) + ((code & 2) ? (int)span - wr : wr);
+        samples[4 * b + 2] = (int)(((uint64_t)r.v[1] * uw) >> 32) + ((code & 1) ? (int)span - wc : wc);
+        samples[4 * b + 3] = code;
+    }
+}
+
 // ---- gather -------------------------------------------------------------------------------------------------------------------
 constexpr int kPairTile = 32, kPairPitch = kPairTile + 1;
 
@@ -105,10 +153,21 @@ struct PairArgs {
     int64_t pool_bytes;
     int n_pairs, ph, pw, scale, swap, lq_tiles, lq_tiles_x, gt_tiles_x;
 };
+struct PairPadArgs : PairArgs {                             // the padded form is chosen by its argument block; the plain one keeps its layout
+    int pad;                                                // the side (LQ pixels) the images are reflected up to
+};
 
-template <int C>
+// cv2.BORDER_REFLECT at the far edge: fedcba|abcdefgh|hgfedcb, any number of periods
+__device__ inline int pairs_reflect(int i, int n) {
+    if (i < n) return i;                                    // every index of an image that needs no padding
+    const int r = i % (2 * n);
+    return r < n ? r : 2 * n - 1 - r;
+}
+
+template <int C, typename Args>
 __global__ void __launch_bounds__(256)
-oss_pairs_gather_kernel(const PairArgs p) {
+oss_pairs_gather_kernel(const Args p) {
+    constexpr bool PAD = std::is_same<Args, PairPadArgs>::value;
     constexpr int kWords = (kPairTile * C + 3) / 4 + 1;     // 4-byte words that cover a tile row at the worst alignment
     __shared__ float tile[C][kPairTile][kPairPitch];
     const int t = threadIdx.x, b = blockIdx.y;
@@ -131,20 +190,26 @@ oss_pairs_gather_kernel(const PairArgs p) {
     int H = (int)lqh * s, W = (int)lqw * s;                 // the image
     if (off < 0 || off > p.pool_bytes || (int64_t)H * W * C > p.pool_bytes - off) H = 0, W = 0, bad = true;
     if ((code & ~7) || ((code & 4) && p.ph != p.pw)) code &= 3, bad = true;
-    const int EH = min(PH, H), EW = min(PW, W);             // rows / columns of the patch that can be read
+    // PAD: the image as the reference's padding() extends it (an image without bytes stays empty: nothing to reflect)
+    int VH = H, VW = W;
+    if constexpr (PAD) {
+        if (H > 0 && W > 0) VH = max(H, p.pad * s), VW = max(W, p.pad * s);
+    }
+    const int EH = min(PH, VH), EW = min(PW, VW);           // rows / columns of the patch that can be read
     const int64_t y64 = (int64_t)top * s, x64 = (int64_t)left * s;
-    if (EH < PH || EW < PW || y64 < 0 || x64 < 0 || y64 > H - EH || x64 > W - EW) bad = true;
-    const int y0 = (int)min(max(y64, (int64_t)0), (int64_t)(H - EH)), xl = (int)min(max(x64, (int64_t)0), (int64_t)(W - EW));
+    if (EH < PH || EW < PW || y64 < 0 || x64 < 0 || y64 > VH - EH || x64 > VW - EW) bad = true;
+    const int y0 = (int)min(max(y64, (int64_t)0), (int64_t)(VH - EH)), xl = (int)min(max(x64, (int64_t)0), (int64_t)(VW - EW));
     if (bad && t == 0) *p.clamped = 1;
     const int th = min(max(EH - r0, 0), kPairTile), tw = min(max(EW - x0, 0), kPairTile);
+    const int tin = PAD ? min(max(W - (xl + x0), 0), tw) : tw;   // columns of the tile that lie inside the image
 
     // 1. source rows -> LDS
     const uint8_t *src = p.pool + off + ((int64_t)(y0 + r0) * W + xl + x0) * C;
-    const int nbytes = tw * C;
+    const int nbytes = tin * C;
     for (int idx = t; idx < kPairTile * kWords; idx += 256) {
         const int r = idx / kWords, j = idx - r * kWords;
         if (r >= th) break;
-        const uint8_t *run = src + (int64_t)r * W * C;
+        const uint8_t *run = PAD ? p.pool + off + ((int64_t)pairs_reflect(y0 + r0 + r, H) * W + xl + x0) * C : src + (int64_t)r * W * C;
         const int head = (int)(reinterpret_cast<uintptr_t>(run) & 3);
         const int k0 = 4 * j - head;                        // position in the run of this word's first byte
         if (k0 >= nbytes) continue;
@@ -162,6 +227,18 @@ oss_pairs_gather_kernel(const PairArgs p) {
             if (k >= 0 && k < nbytes) {
                 const int x = k / C, c = k - x * C;
                 tile[(C == 3 && p.swap) ? 2 - c : c][r][x] = (float)((w >> (8 * i)) & 255u) / 255.0f;
+            }
+        }
+    }
+    if constexpr (PAD) {                                    // the reflected columns: one pixel per thread, bytes of the image only
+        if (tin < tw) {
+            const uint8_t *img = p.pool + off;
+            for (int idx = t; idx < kPairTile * kPairTile; idx += 256) {
+                const int r = idx / kPairTile, x = idx % kPairTile;
+                if (r >= th || x < tin || x >= tw) continue;
+                const uint8_t *px = img + ((int64_t)pairs_reflect(y0 + r0 + r, H) * W + pairs_reflect(xl + x0 + x, W)) * C;
+#pragma unroll
+                for (int c = 0; c < C; ++c) tile[(C == 3 && p.swap) ? 2 - c : c][r][x] = (float)px[c] / 255.0f;
             }
         }
     }
@@ -189,6 +266,25 @@ static int pairs_ok(int channels, int scale, int ph, int pw, int batch) {
     if ((int64_t)ph * scale > (1 << 20) || (int64_t)pw * scale > (1 << 20)) return 0;
     const int64_t tiles = (int64_t)pair_tiles(ph) * pair_tiles(pw) + (int64_t)pair_tiles(ph * scale) * pair_tiles(pw * scale);
     return tiles <= 65535;
+}
+
+template <typename Args>
+static int pairs_gather_launch(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq,
+                               float *gt, int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb,
+                               int pad_to, oss_stream_t stream) {
+    if (!pool || !table || !samples || !lq || !gt || !clamped) return OSS_ERR_NULL;
+    if (!pairs_ok(channels, scale, patch_h, patch_w, batch) || n_pairs < 1 || pool_bytes < 1) return OSS_ERR_SHAPE;
+    Args p;
+    p.pool = static_cast<const uint8_t *>(pool), p.table = table, p.samples = samples, p.lq = lq, p.gt = gt, p.clamped = clamped;
+    p.pool_bytes = pool_bytes, p.n_pairs = n_pairs, p.ph = patch_h, p.pw = patch_w, p.scale = scale, p.swap = swap_rb ? 1 : 0;
+    p.lq_tiles_x = pair_tiles(patch_w), p.gt_tiles_x = pair_tiles(patch_w * scale);
+    p.lq_tiles = pair_tiles(patch_h) * p.lq_tiles_x;
+    if constexpr (std::is_same<Args, PairPadArgs>::value) p.pad = pad_to;
+    const dim3 grid(p.lq_tiles + pair_tiles(patch_h * scale) * p.gt_tiles_x, batch);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (channels == 3) hipLaunchKernelGGL((oss_pairs_gather_kernel<3, Args>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((oss_pairs_gather_kernel<1, Args>), grid, dim3(256), 0, s, p);
+    return (int)hipGetLastError();
 }
 
 }  // namespace oss
@@ -219,20 +315,32 @@ int oss_pairs_draw(const int64_t *table, int n_pairs, int64_t *counter, int *sam
     return (int)hipGetLastError();
 }
 
+int oss_pairs_draw_window(const int64_t *table, int n_pairs, int64_t *counter, int *samples, int batch, int patch, int full_patch,
+                          int pad_to, int64_t seed, int rank, int world, int flags, oss_stream_t stream) {
+    if (!table || !counter || !samples) return OSS_ERR_NULL;
+    if (n_pairs < 1 || batch < 1 || patch < 1 || full_patch < patch || full_patch > (1 << 20) || pad_to < 0 || pad_to > (1 << 20) ||
+        world < 1 || rank < 0 || rank >= world || (flags & ~(OSS_PAIRS_HFLIP | OSS_PAIRS_ROT)))
+        return OSS_ERR_SHAPE;
+    const int code_mask = ((flags & OSS_PAIRS_HFLIP) ? 1 : 0) | ((flags & OSS_PAIRS_ROT) ? 6 : 0);
+    hipLaunchKernelGGL(oss_pairs_draw_window_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, n_pairs,
+                       counter, samples, batch, patch, full_patch, pad_to, (uint32_t)(uint64_t)seed, (uint32_t)((uint64_t)seed >> 32),
+                       rank, world, code_mask);
+    return (int)hipGetLastError();
+}
+
 int oss_pairs_gather(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq, float *gt,
                      int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb, oss_stream_t stream) {
-    if (!pool || !table || !samples || !lq || !gt || !clamped) return OSS_ERR_NULL;
-    if (!pairs_ok(channels, scale, patch_h, patch_w, batch) || n_pairs < 1 || pool_bytes < 1) return OSS_ERR_SHAPE;
-    PairArgs p;
-    p.pool = static_cast<const uint8_t *>(pool), p.table = table, p.samples = samples, p.lq = lq, p.gt = gt, p.clamped = clamped;
-    p.pool_bytes = pool_bytes, p.n_pairs = n_pairs, p.ph = patch_h, p.pw = patch_w, p.scale = scale, p.swap = swap_rb ? 1 : 0;
-    p.lq_tiles_x = pair_tiles(patch_w), p.gt_tiles_x = pair_tiles(patch_w * scale);
-    p.lq_tiles = pair_tiles(patch_h) * p.lq_tiles_x;
-    const dim3 grid(p.lq_tiles + pair_tiles(patch_h * scale) * p.gt_tiles_x, batch);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (channels == 3) hipLaunchKernelGGL(oss_pairs_gather_kernel<3>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(oss_pairs_gather_kernel<1>, grid, dim3(256), 0, s, p);
-    return (int)hipGetLastError();
+    return pairs_gather_launch<PairArgs>(pool, pool_bytes, table, n_pairs, samples, lq, gt, clamped, batch, channels, patch_h, patch_w,
+                                      scale, swap_rb, 0, stream);
+}
+
+int oss_pairs_gather_padded(const void *pool, int64_t pool_bytes, const int64_t *table, int n_pairs, const int *samples, float *lq,
+                            float *gt, int *clamped, int batch, int channels, int patch_h, int patch_w, int scale, int swap_rb,
+                            int pad_to, oss_stream_t stream) {
+    // the reference pads LQ and GT by the same pixel count: a pair only at scale 1
+    if (pad_to < 0 || pad_to > (1 << 20) || (pad_to > 0 && scale != 1)) return OSS_ERR_SHAPE;
+    return pairs_gather_launch<PairPadArgs>(pool, pool_bytes, table, n_pairs, samples, lq, gt, clamped, batch, channels, patch_h, patch_w,
+                                     scale, swap_rb, pad_to, stream);
 }
 
 }  // extern "C"

@@ -39,5 +39,5 @@ from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gat
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401
 from .losses import pixel_loss_bwd, pixel_loss_fwd, pixel_loss_ok  # noqa: F401
 from .metrics import image_metrics, image_metrics_ok  # noqa: F401
-from .pairs import pairs_draw, pairs_gather, pairs_ok  # noqa: F401
+from .pairs import pairs_draw, pairs_draw_window, pairs_gather, pairs_gather_padded, pairs_ok  # noqa: F401
 from .scan import merge4, selective_scan_bwd, selective_scan_fwd  # noqa: F401
