@@ -741,6 +741,40 @@ int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, d
                       int64_t b_batch_stride, int64_t b_channel_stride, int64_t b_row_stride, int crop_border, int flags,
                       oss_stream_t stream);
 
+/* The features of the reference's NIQE, the no-reference quality metric (Deraining/basicsr/metrics/niqe.py:10-140), of a batch of
+ * images on the device, in one launch (oss_niqe.hip): the plane is cropped to whole 96 x 96 blocks from the top-left and every
+ * block gives 18 features at scale 1 and 18 at scale 2 (the plane halved by 2 x 2 means, blocks of 48 x 48) -- per scale an AGGD
+ * fit of the block of the MSCN map (7 x 7 window, 'nearest' border) and of its product with the block rolled by [0, 1], [1, 0],
+ * [1, 1], [1, -1] inside itself.  The multivariate-Gaussian distance of niqe.py:142-155 is left to the host (36 x 36, per image).
+ *   a         (batch, channels, height, width), channels 1 or 3 in R, G, B order, element strides for batch / channel / row, column
+ *             stride 1 (cropped views need no copy); io = fp32 / fp16 / bf16
+ *   tables    (4, OSS_NIQE_GRID) doubles in DEVICE memory on the grid gam = arange(0.2, 10.001, 0.001) of estimate_aggd_param: gam,
+ *             r_gam = G(2/gam)^2 / (G(1/gam) G(3/gam)) (increasing), sqrt(G(1/gam) / G(3/gam)), G(2/gam) / G(1/gam).  The caller
+ *             computes them once in double; no gamma function is evaluated on the device
+ *   window    the 7 x 7 window of the pristine model, 49 doubles in HOST memory, row-major, as scipy.ndimage.convolve receives it
+ *             (the launcher flips it); read before the call returns
+ *   out       (batch, blocks, OSS_NIQE_FEATURES) doubles, blocks = (height' / 96) * (width' / 96) in the reference's order
+ *             (block column outer, block row inner); features 0-17 scale 1, 18-35 scale 2: alpha, (beta_l + beta_r) / 2, then
+ *             four times alpha, mean, beta_l, beta_r.  A block whose MSCN values are all zero has alpha 0.2 and NaN elsewhere,
+ *             as in the reference (argmin of an all-NaN array)
+ *   crop_border pixels are dropped on every side first (niqe.py:200-201)
+ *   flags     OSS_METRIC_QUANTISE, OSS_METRIC_Y as for oss_image_metrics; the metric is defined on ONE plane, so three channels
+ *             need OSS_METRIC_Y and one channel must not set it
+ * Dtypes follow the reference: fp32 planes, every window sum 49 products and additions in fp64 rounded once to fp32, the other
+ * steps up to the MSCN map and the products single correctly rounded fp32 operations, the moments fp64 sums of those fp32 values
+ * in a fixed order (the reference sums them in fp32: its features are 1e-7 away).  No atomics, no scratch: reruns are
+ * bit-identical, an image's result does not depend on the batch, no host read-back, capturable into a hipGraph.
+ * oss_niqe_features_ok is a pure host query: 1 when the element type, shape and flags are taken.  OSS_ERR_NULL for a NULL pointer,
+ * OSS_ERR_SHAPE for io no element type, channels not in {1, 3}, OSS_METRIC_Y that does not go with the channels, an unknown flag, a
+ * cropped plane under 96 pixels on a side, or a launch grid beyond the device limits (batch > 65535, blocks > 2^31 - 1). */
+#define OSS_NIQE_BLOCK 96
+#define OSS_NIQE_FEATURES 36
+#define OSS_NIQE_GRID 9801
+int oss_niqe_features_ok(int channels, int height, int width, int crop_border, int flags, oss_dtype io);
+int oss_niqe_features(oss_dtype io, const void *a, const double *tables, const double *window, double *out, int batch, int channels,
+                      int height, int width, int64_t a_batch_stride, int64_t a_channel_stride, int64_t a_row_stride, int crop_border,
+                      int flags, oss_stream_t stream);
+
 /* The reference's pixel losses with their gradients on the device (oss_pixel_loss.hip): L1Loss, MSELoss, PSNRLoss (with toY) and
  * CharbonnierLoss of Deraining/basicsr/models/losses/losses.py:26-122 with the weighting and reduction of weight_reduce_loss
  * (losses/loss_util.py:25-54).  lw = loss_weight, d = pred - target, n = batch * channels * plane:

@@ -805,6 +805,17 @@ int oss_image_metrics(oss_dtype io, const void *a, const void *b, double *out, d
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+int oss_niqe_features_ok(int channels, int height, int width, int crop_border, int flags, oss_dtype io) {
+    return niqe_features_ok(channels, height, width, crop_border, flags, io);
+}
+int oss_niqe_features(oss_dtype io, const void *a, const double *tables, const double *window, double *out, int batch, int channels,
+                      int height, int width, int64_t asb, int64_t asc, int64_t ars, int crop_border, int flags, oss_stream_t stream) {
+    if (is_f32_split(io)) return OSS_ERR_SHAPE;
+    if (!a || !tables || !window || !out) return OSS_ERR_NULL;
+    return niqe_features(io, a, tables, window, out, batch, channels, height, width, asb, asc, ars, crop_border, flags,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 size_t oss_pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t batch, int64_t channels,
                                       int64_t plane) {
     return pixel_loss_partial_doubles(kind, flags, pred_io, target_io, batch, channels, plane);

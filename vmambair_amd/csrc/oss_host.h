@@ -218,6 +218,10 @@ int image_metrics_ok(oss_dtype io, int C, int H, int W, int crop, int flags);
 size_t image_metrics_partial_doubles(int B, int C, int H, int W, int crop);
 int image_metrics(oss_dtype io, const void *a, const void *b, double *out, double *part, int B, int C, int H, int W, int64_t asb,
                   int64_t asc, int64_t ars, int64_t bsb, int64_t bsc, int64_t brs, int crop, int flags, hipStream_t s);
+// NIQE features of a batch of images (oss_niqe.hip); window: 49 doubles in host memory
+int niqe_features_ok(int C, int H, int W, int crop, int flags, oss_dtype io);
+int niqe_features(oss_dtype io, const void *a, const double *tables, const double *window, double *out, int B, int C, int H, int W,
+                  int64_t asb, int64_t asc, int64_t ars, int crop, int flags, hipStream_t s);
 // pixel losses with their gradients (oss_pixel_loss.hip); N, C, plane = batch, channels, H * W
 size_t pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t N, int64_t C, int64_t plane);
 size_t pixel_loss_stat_doubles(int kind, int flags, int64_t N, int64_t C, int64_t plane);

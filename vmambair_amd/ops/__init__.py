@@ -9,7 +9,8 @@ One module per operator family (round 1 had a single 1 000-line ``ops.py``):
   ``conv3x3``   dense 3x3 convolutions with <= 4 channels on one side (patch_embed, the tail's last layer); opt-in MFMA kernels
                 for the GEMM-shaped ones of the skeleton (Downsample, Upsample, the x4 tail)
   ``dwconv``    depth-wise 3x3 (+ silu)          ``layernorm``  NCHW LayerNorm (+ gate)          ``ffn``  gelu gate of the EFFN
-  ``metrics``   validation PSNR + SSIM of a batch of image pairs in one call (mean squared error, mean SSIM; fp64 on the device)
+  ``metrics``   validation PSNR + SSIM of a batch of image pairs in one call (mean squared error, mean SSIM; fp64 on the device); the
+                features of the no-reference NIQE per 96 x 96 block of a batch of images
   ``losses``    the pixel losses (L1, MSE, Charbonnier, PSNR) with their gradient w.r.t. the prediction: fp64 sums in a fixed order
   ``pairs``     training batches cut from a device-resident pool of image pairs: counter-based draw + one crop / flip / convert launch
   ``_common``   dtype table, checks, deferred finishing, weight-gradient side stream
@@ -38,6 +39,6 @@ from .conv3x3 import conv3x3 as conv3x3_layer  # noqa: F401
 from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gate, gelu_gate_bwd, gelu_gate_fwd  # noqa: F401
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401
 from .losses import pixel_loss_bwd, pixel_loss_fwd, pixel_loss_ok  # noqa: F401
-from .metrics import image_metrics, image_metrics_ok  # noqa: F401
+from .metrics import image_metrics, image_metrics_ok, niqe_features, niqe_features_ok  # noqa: F401
 from .pairs import pairs_draw, pairs_draw_window, pairs_gather, pairs_gather_padded, pairs_ok  # noqa: F401
 from .scan import merge4, selective_scan_bwd, selective_scan_fwd  # noqa: F401

@@ -2,7 +2,9 @@
 the reference's ``calculate_psnr`` (Deraining/basicsr/metrics/psnr_ssim.py:9-63) and the mean SSIM of ``_ssim`` (:66-99;
 Deraining/Deraining/utils.py:31-78) or ``_ssim_cly`` (:184-222) of a batch of image pairs in one call, with ``tensor2img``'s
 quantisation (SRGAN/VmambaIR/utils/img_util.py:68-92) and ``to_y_channel`` (metrics/metric_util.py:34-47) applied on load.
-``vmambair_amd.metrics`` is the public face (PSNR in dB, the reference's signatures); flags as in include/vmambair_oss.h."""
+``vmambair_amd.metrics`` is the public face (PSNR in dB, the reference's signatures); flags as in include/vmambair_oss.h.
+``torch.ops.vmambair.niqe_features`` on ``oss_niqe.hip``: the per-block features of the reference's no-reference metric ``niqe``
+(Deraining/basicsr/metrics/niqe.py:10-140) of a batch of images in one launch, with the same load."""
 from __future__ import annotations
 
 import torch
@@ -47,5 +49,41 @@ def image_metrics(a: torch.Tensor, b: torch.Tensor, crop_border: int, flags: int
     return out
 
 
+def niqe_features_ok(a: torch.Tensor, crop_border: int, flags: int) -> bool:
+    """whether ``niqe_features`` takes this (batch, 1 | 3, H, W) tensor with these flags (a host query of the library)"""
+    if not (a.is_cuda and a.dim() == 4 and a.dtype in _DT and a.numel()):
+        return False
+    return bool(_capi.load().oss_niqe_features_ok(a.shape[1], a.shape[2], a.shape[3], int(crop_border), int(flags), _DT[a.dtype]))
+
+
+def niqe_features(a: torch.Tensor, tables: torch.Tensor, window: torch.Tensor, crop_border: int, flags: int) -> torch.Tensor:
+    """a (batch, 1 | 3, H, W) RGB, fp32 / fp16 / bf16 -> (batch, blocks, 36) float64 on the device: the features of the reference's
+    ``niqe`` (niqe.py:101-140) for every 96 x 96 block of the cropped plane, blocks in the reference's order.  ``tables``: the
+    (4, 9801) float64 tensor of ``metrics.NiqeModel`` on ``a``'s device; ``window``: its 7 x 7 float64 window on the HOST (it
+    travels in the kernel's arguments).  One launch on the current stream, no host synchronisation, no scratch, bit-reproducible;
+    the call can be captured into a graph."""
+    _check(a.is_cuda and tables.is_cuda and tables.device == a.device, "niqe_features: a and tables must be CUDA/HIP tensors on one device")
+    _check(a.dim() == 4 and a.dtype in _DT, "niqe_features: a must be a (batch, channels, H, W) fp32, fp16 or bf16 tensor")
+    _check(tables.dtype == torch.float64 and tuple(tables.shape) == (4, _capi.NIQE_GRID) and tables.is_contiguous(),
+           f"niqe_features: tables must be a contiguous (4, {_capi.NIQE_GRID}) float64 tensor (metrics.NiqeModel.device_tables)")
+    _check(not window.is_cuda and window.dtype == torch.float64 and tuple(window.shape) == (7, 7),
+           "niqe_features: window must be a 7 x 7 float64 tensor on the host")
+    B, C, H, W = a.shape
+    lib = _capi.load()
+    _check(B > 0 and lib.oss_niqe_features_ok(C, H, W, int(crop_border), int(flags), _DT[a.dtype]),
+           f"niqe_features: shape {tuple(a.shape)} with crop_border {crop_border} and flags {flags} is not supported (1 channel, or 3 "
+           "with the Y flag; the cropped plane holds a 96 x 96 block)")
+    a, window = _rows(a.detach()), window.contiguous()
+    blocks = ((H - 2 * int(crop_border)) // _capi.NIQE_BLOCK) * ((W - 2 * int(crop_border)) // _capi.NIQE_BLOCK)
+    out = torch.empty((B, blocks, _capi.NIQE_FEATURES), dtype=torch.float64, device=a.device)
+    with torch.cuda.device(a.device):
+        _capi.check(lib.oss_niqe_features(_DT[a.dtype], a.data_ptr(), tables.data_ptr(), window.data_ptr(), out.data_ptr(), B, C, H, W,
+                                          a.stride(0), a.stride(1), a.stride(2), int(crop_border), int(flags),
+                                          torch.cuda.current_stream().cuda_stream), "oss_niqe_features")
+    return out
+
+
 _LIB.define("image_metrics(Tensor a, Tensor b, int crop_border, int flags) -> Tensor")
 _LIB.impl("image_metrics", image_metrics, "CUDA")
+_LIB.define("niqe_features(Tensor a, Tensor tables, Tensor window, int crop_border, int flags) -> Tensor")
+_LIB.impl("niqe_features", niqe_features, "CUDA")
