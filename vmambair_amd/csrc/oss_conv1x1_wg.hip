@@ -415,7 +415,8 @@ struct WgLnBwdArgs {
 
 // The LayerNorm-backward stage shared by the two kernels below: dn for all M channels of the workgroup's PT pixels in `os`
 // ([4 tiles][32][PITCH]), the LayerNorm input tile in `xt` and the skip gradient in `st` ([M][PITCH] each), `red` = [2][NPART][PT] floats.
-template <typename T, int PT>
+// BF: the BiasFree form, with x - mu - mean_c(x - mu) in dx as oss_ln_nchw_bwd_kernel (the rounding of the stored mean).
+template <typename T, int PT, bool BF>
 __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T *os, const T *xt, const T *st, float *red, int M, int P,
                                                int b, int p0, int tid, int lane) {
     constexpr int PITCH = PT + 8;
@@ -431,6 +432,7 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
         rs[0] = r4.x; rs[1] = r4.y; rs[2] = r4.z; rs[3] = r4.w;
     }
     float gv[CMAX][4], xv[CMAX][4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    float s3[4] = {0.f, 0.f, 0.f, 0.f};   // (BF) sum_c (x - mu)
     // (round 4) the LayerNorm weights of this thread's channels, all requested here (clamped index, no branch).  Read where they are
     // used -- `if (c < M) { wc = a.w[c]; ...` in both loops below -- each was a branch + load + s_waitcnt vmcnt(0): 2 x 16 dependent
     // round trips in a kernel that runs one or two workgroups per CU.
@@ -457,6 +459,7 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
                 const float gw = gg * wc;
                 s1[u] += gw;
                 s2[u] = __builtin_fmaf(gw, with_bias ? xh : xv[i][u], s2[u]);
+                if constexpr (BF) s3[u] += xv[i][u] - mu[u];
             }
         } else {
 #pragma unroll
@@ -478,6 +481,19 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) { m1[u] /= (float)M; m2[u] /= (float)M; }
+    if constexpr (BF) {
+        __syncthreads();   // everyone has read red
+        *reinterpret_cast<f32x4 *>(red + part * PT + px) = f32x4{s3[0], s3[1], s3[2], s3[3]};
+        __syncthreads();
+        s3[0] = s3[1] = s3[2] = s3[3] = 0.f;
+#pragma unroll
+        for (int q = 0; q < NPART; ++q) {
+            const f32x4 t3 = *reinterpret_cast<const f32x4 *>(red + q * PT + px);
+            s3[0] += t3.x; s3[1] += t3.y; s3[2] += t3.z; s3[3] += t3.w;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s3[u] /= (float)M;
+    }
     T *dxb = a.dx + (size_t)b * M * P + p0;
 #pragma unroll
     for (int i = 0; i < CMAX; ++i) {
@@ -492,7 +508,7 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
             float d[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float xh = (xv[i][u] - mu[u]) * rs[u];
+                const float xh = BF ? ((xv[i][u] - mu[u]) - s3[u]) * rs[u] : (xv[i][u] - mu[u]) * rs[u];
                 const float gw = gv[i][u] * wc;
                 d[u] = (with_bias ? rs[u] * (gw - m1[u] - xh * m2[u]) : rs[u] * gw - xh * rs[u] * rs[u] * m2[u]) + sk[u];
             }
@@ -504,7 +520,7 @@ __device__ __forceinline__ void wg_lnbwd_stage(const WgLnBwdArgs<T> &a, const T 
 // (The image form of the weight fragments (oss_conv1x1_wg_kernel's WIMG) was built for this kernel too, bit-identical, and measured no
 // gain -- 18.4 against 18.5 us at 192 -> 96, 11.7 against 11.7 at 96 -> 48, profiles/conv1x1_packed_weights_ab.txt: its one group of
 // weight loads is in flight across the copy of the dy tile either way -- so it reads the fp32 weights as before.)
-template <typename T, int KS, int PT>
+template <typename T, int KS, int PT, bool BF>
 __global__ void __launch_bounds__(256)
 oss_conv1x1_dgrad_lnbwd_kernel(const T *__restrict__ dy, const float *__restrict__ w, int M, int P, int64_t xsb, int64_t xsk,
                                WgLnBwdArgs<T> a) {
@@ -585,7 +601,7 @@ oss_conv1x1_dgrad_lnbwd_kernel(const T *__restrict__ dy, const float *__restrict
         }
     }
     __syncthreads();
-    wg_lnbwd_stage<T, PT>(a, os, xt, st, red, M, P, b, p0, tid, lane);
+    wg_lnbwd_stage<T, PT, BF>(a, os, xt, st, red, M, P, b, p0, tid, lane);
 }
 
 __global__ void __launch_bounds__(256)
@@ -615,14 +631,15 @@ static int lnbwd_launch(const T *dy, const float *w, int B, int M, int K, int P,
     const int pt = (long)B * (P / 128) >= 256 ? 128 : 64;
     const size_t smem = sizeof(uint16_t) * ((size_t)K + 4 * 32) * (pt + 8) + sizeof(float) * 2 * 8 * 128;
     dim3 grid(P / pt, B);
-#define OSS_LNB(KS_, PT_)                                                                                   \
+#define OSS_LNB(KS_, PT_, BF_)                                                                              \
     do {                                                                                                    \
         static LdsGate gate;                                                                                \
-        auto kern = oss_conv1x1_dgrad_lnbwd_kernel<T, KS_, PT_>;                                            \
+        auto kern = oss_conv1x1_dgrad_lnbwd_kernel<T, KS_, PT_, BF_>;                                       \
         if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;                \
         hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, dy, w, M, P, xsb, xsk, a);                       \
     } while (0)
-#define OSS_LNB2(KS_) do { if (pt == 128) OSS_LNB(KS_, 128); else OSS_LNB(KS_, 64); } while (0)
+#define OSS_LNB1(KS_, PT_) do { if (a.with_bias) OSS_LNB(KS_, PT_, false); else OSS_LNB(KS_, PT_, true); } while (0)
+#define OSS_LNB2(KS_) do { if (pt == 128) OSS_LNB1(KS_, 128); else OSS_LNB1(KS_, 64); } while (0)
     switch (K / 16) {
         case 2: OSS_LNB2(2); break;
         case 3: OSS_LNB2(3); break;
@@ -633,6 +650,7 @@ static int lnbwd_launch(const T *dy, const float *w, int B, int M, int K, int P,
         default: return OSS_ERR_SHAPE;
     }
 #undef OSS_LNB2
+#undef OSS_LNB1
 #undef OSS_LNB
     const int nblk = (int)(grid.x * grid.y);
     if (defer_finish())

@@ -157,9 +157,15 @@ oss_ln_nchw_fwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, co
 //   WithBias: xhat = (x-mu) rstd;  g = dy w;  dx = rstd (g - mean(g) - xhat mean(g xhat))
 //   BiasFree: y = x rstd w, rstd = (var+eps)^-1/2 with var around mu:
 //             dx = rstd g - (x - mu) rstd^3 mean(g x)
+//             Here x - mu is multiplied by rstd^3 mean(g x), which does not shrink with the variance (x is not centred): at
+//             var << eps (rstd ~ 316) the rounding of the STORED fp32 mean alone, |mu| 2^-24, put 2 % of |dx| into dx (24000 x
+//             the error of fp32 autograd on the same formula: tests/test_ln_regimes_gpu.py, regime `flat`).  So this form
+//             (MODE bit 1) takes x - mu - mean_c(x - mu): the mean of the residuals IS that rounding error, to fp32 relative
+//             precision.  The WithBias instantiations are the code they were.
+// MODE: bit 0 = the gated form, bit 1 = BiasFree with the correction above (launched exactly when bias == NULL).
 // A channel belongs to one wave, so its dweight / dbias partial is a plain 64-lane sum, stored straight
 // to part[blk][2][C].
-template <typename TX, typename TY, bool GATE, int CPW, int V, int MAXT>
+template <typename TX, typename TY, int MODE, int CPW, int V, int MAXT>
 __global__ void __launch_bounds__(MAXT)
 oss_ln_nchw_bwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
                        const TY *__restrict__ gate, const TY *__restrict__ dy, const float *__restrict__ mean_in,
@@ -171,6 +177,7 @@ oss_ln_nchw_bwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, co
                        gradient that enters is dy * (1 + dy_mul[b, c]) + add_scale * dy_add[b, c] (dy_mul NULL: dy + ...), both
                        (B, C) -- the backward of SS2D_1's channel gate (y2 * c + y2 with c a function of mean_hw(y2)) folded into
                        this kernel's load instead of a pass of its own */) {
+    constexpr bool GATE = (MODE & 1) != 0, BF = (MODE & 2) != 0;
     __shared__ float red[2][kLnMaxWaves * 64 * V];
     // per-channel dweight / dbias partials of this workgroup, staged here and written out in one coalesced pass: stored
     // to global memory channel by channel inside the first pass, every store dragged an s_waitcnt vmcnt behind it that
@@ -200,9 +207,9 @@ oss_ln_nchw_bwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, co
     const float okf = ok ? 1.f : 0.f;
     float *pw_out = part + (size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
     float xv[NI][V], gv[NI][V], zv[NI][V], rv[NI][V];  // x, dy, gate, res
-    float s1[V], s2[V];
+    float s1[V], s2[V], s3[V];   // s3 (BF): sum_c (x - mu)
 #pragma unroll
-    for (int u = 0; u < V; ++u) { s1[u] = 0.f; s2[u] = 0.f; }
+    for (int u = 0; u < V; ++u) { s1[u] = 0.f; s2[u] = 0.f; s3[u] = 0.f; }
     // the wave's weights and biases as ONE vector load each (lane i = channel slot i): a scalar load per channel, waited for
     // inside the pass, was a round trip per channel
     float wvec = 0.f, bvec = 0.f, mvec = 1.f, avec = 0.f;
@@ -228,6 +235,7 @@ oss_ln_nchw_bwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, co
             const float gw = g * wc;
             s1[u] += gw;
             s2[u] = __builtin_fmaf(gw, with_bias ? xh : xval[u], s2[u]);
+            if constexpr (BF) s3[u] += xval[u] - mu[u];
         }
         const float pw = segment_sum_to_last<64>(aw);
         const float pb = segment_sum_to_last<64>(ab);
@@ -292,13 +300,18 @@ oss_ln_nchw_bwd_kernel(const TX *__restrict__ x, const float *__restrict__ w, co
     float m1[V], m2[V];
 #pragma unroll
     for (int u = 0; u < V; ++u) { m1[u] = s1[u] / (float)C; m2[u] = s2[u] / (float)C; }
+    if constexpr (BF) {   // (red[0] is free again: everyone read it before the barrier of the second sum)
+        ln_cross_wave_sum<V>(red[0], s3, wave, lane, nw);
+#pragma unroll
+        for (int u = 0; u < V; ++u) s3[u] /= (float)C;
+    }
     TX *dxp = dx + (size_t)b * C * P + pc;
     TY *dgp = GATE ? dgate + (size_t)b * dgsb + pc : nullptr;
     auto second = [&](int c, float wc, float bc, const float (&xval)[V], const float (&gy)[V], const float (&zval)[V], const float (&rval)[V]) {
         float d[V], dg[V];
 #pragma unroll
         for (int u = 0; u < V; ++u) {
-            const float xh = (xval[u] - mu[u]) * rstd[u];
+            const float xh = BF ? ((xval[u] - mu[u]) - s3[u]) * rstd[u] : (xval[u] - mu[u]) * rstd[u];
             float g = gy[u];
             if constexpr (GATE) {
                 const float sg = __builtin_amdgcn_rcpf(1.f + exp2_hw(-zval[u] * kLog2e));  // sigmoid(z)
@@ -433,8 +446,10 @@ static int ln_bwd_t(const void *x, const float *w, const float *bias, const void
     const TY *dyp = reinterpret_cast<const TY *>(dy);
     TX *dxp = reinterpret_cast<TX *>(dx);
     TY *dgp = reinterpret_cast<TY *>(dgate);
-    if (gate) OSS_LN_LAUNCH(oss_ln_nchw_bwd_kernel, true, xp, w, bias, gp, dyp, mean, rstd, dxp, dgp, part, C, P, xsb, xsc, gsb, gsc, rp, dgsb, dy_mul, dy_add, add_scale);
-    else      OSS_LN_LAUNCH(oss_ln_nchw_bwd_kernel, false, xp, w, bias, gp, dyp, mean, rstd, dxp, dgp, part, C, P, xsb, xsc, gsb, gsc, rp, dgsb, dy_mul, dy_add, add_scale);
+#define OSS_LN_BWD(MODE_) OSS_LN_LAUNCH(oss_ln_nchw_bwd_kernel, MODE_, xp, w, bias, gp, dyp, mean, rstd, dxp, dgp, part, C, P, xsb, xsc, gsb, gsc, rp, dgsb, dy_mul, dy_add, add_scale)
+    if (bias) { if (gate) OSS_LN_BWD(1); else OSS_LN_BWD(0); }
+    else      { if (gate) OSS_LN_BWD(3); else OSS_LN_BWD(2); }
+#undef OSS_LN_BWD
     if (defer_finish())
         defer_sum(part, nblk, (size_t)2 * C, (size_t)(db ? 2 : 1) * C, dw, (size_t)C, db);
     else
