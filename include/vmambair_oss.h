@@ -775,6 +775,42 @@ int oss_niqe_features(oss_dtype io, const void *a, const double *tables, const d
                       int height, int width, int64_t a_batch_stride, int64_t a_channel_stride, int64_t a_row_stride, int crop_border,
                       int flags, oss_stream_t stream);
 
+/* The two custom operators of the RealSR degradation pipeline on the device (oss_degrade.hip; MambaRealSR.feed_data,
+ * RealSR/VmambaIR/models/MambaRealSR_model.py:146-263): filter2D and USMSharp of the basicsr package.  All tensors are dense fp32
+ * (batch, channels, H, W), sums are fp32; out must not overlap img.  An axis of n elements is padded by k / 2 with torch's 'reflect'
+ * rule inside the load (index -v for v < 0, 2n - 2 - v from n on); no padded copy exists.
+ *   oss_filter2d    out[b,c,y,x] = sum_ij kernel[b or 0][i][j] * pad[b,c,y+i,x+j]: cross-correlation, no flip.  kernel is
+ *                   (kernels, k, k) with kernels == 1 (shared) or == batch (one per sample, shared by its channels), k odd <= 21.
+ *                   A workgroup finds the non-zero bounding box of its kernel on the device and leaves the zero taps out, which
+ *                   changes nothing for finite input.  epilogue: OSS_FILTER_NONE; OSS_FILTER_CLAMP = clamp to [0, 1];
+ *                   OSS_FILTER_QUANTISE = clamp(rint(x * 255), 0, 255) / 255 with round-half-even and the division as torch
+ *                   evaluates it on the device, q * fp32(1 / 255), so that it equals torch's expression there bit for bit.  One launch.
+ *   oss_filter_sep  the same correlation with the rank-1 kernel g g^T of one odd vector g (k <= 63): a row pass into scratch
+ *                   (oss_filter_sep_scratch_floats floats), a column pass into out.  Two launches.
+ *   oss_usm_sharp   blur = filter_sep(img); residual = img - blur; mask = (|residual| * 255 > threshold) as 0 / 1;
+ *                   soft = filter_sep(mask); sharp = clip(img + weight * residual, 0, 1); out = img + soft * (sharp - img), which is
+ *                   soft * sharp + (1 - soft) * img and returns img itself where weight == 0 or the mask is empty.  Four launches;
+ *                   mask (may be NULL) receives the 0 / 1 mask; scratch: oss_usm_scratch_floats floats, no init.
+ * Nothing is allocated or read back: every call can be captured into a hipGraph.  The three size queries are pure host calls and
+ * the support queries: 0 when the shape is not taken -- k even, k < 1 or above the limit, H <= k / 2 or W <= k / 2 (one
+ * reflection is then not enough), a dimension < 1 or above 2^24, kernels neither 1 nor batch, more than 2^31 - 1 workgroups.
+ * The entry points return OSS_ERR_SHAPE for the same and for an unknown epilogue, OSS_ERR_NULL for a missing pointer, without a
+ * launch. */
+#define OSS_FILTER_NONE 0
+#define OSS_FILTER_CLAMP 1
+#define OSS_FILTER_QUANTISE 2
+#define OSS_FILTER2D_MAX_K 21
+#define OSS_FILTER_SEP_MAX_K 63
+size_t oss_filter2d_workgroups(int64_t batch, int64_t channels, int64_t h, int64_t w, int k, int64_t kernels);
+int oss_filter2d(const float *img, const float *kernel, float *out, int64_t batch, int64_t channels, int64_t h, int64_t w, int k,
+                 int64_t kernels, int epilogue, oss_stream_t stream);
+size_t oss_filter_sep_scratch_floats(int64_t batch, int64_t channels, int64_t h, int64_t w, int k);
+int oss_filter_sep(const float *img, const float *g, float *out, float *scratch, int64_t batch, int64_t channels, int64_t h,
+                   int64_t w, int k, oss_stream_t stream);
+size_t oss_usm_scratch_floats(int64_t batch, int64_t channels, int64_t h, int64_t w, int k);
+int oss_usm_sharp(const float *img, const float *g, float *out, float *mask, float *scratch, int64_t batch, int64_t channels,
+                  int64_t h, int64_t w, int k, float weight, float threshold, oss_stream_t stream);
+
 /* The reference's pixel losses with their gradients on the device (oss_pixel_loss.hip): L1Loss, MSELoss, PSNRLoss (with toY) and
  * CharbonnierLoss of Deraining/basicsr/models/losses/losses.py:26-122 with the weighting and reduction of weight_reduce_loss
  * (losses/loss_util.py:25-54).  lw = loss_weight, d = pred - target, n = batch * channels * plane:

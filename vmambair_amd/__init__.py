@@ -12,9 +12,11 @@ from . import _capi  # noqa: F401  (loads the C-ABI library lazily; import never
 from ._precision import (float32_matmul_precision, get_float32_matmul_precision,  # noqa: F401
                          set_float32_matmul_precision)
 from .data import DevicePairPool, ProgressiveSchedule  # noqa: F401
+from . import degradations  # noqa: F401  filter2D, USMSharp and the training pair pool of the RealSR degradation pipeline
 from . import losses  # noqa: F401  the reference's pixel losses (L1, MSE, PSNR, Charbonnier) on the device
 from .ops import selective_scan_fwd, selective_scan_bwd, scan_chunk  # noqa: F401
 from .selective_scan import SelectiveScanFn, selective_scan_fn  # noqa: F401
 
 __all__ = ["selective_scan_fwd", "selective_scan_bwd", "scan_chunk", "SelectiveScanFn", "selective_scan_fn",
-           "set_float32_matmul_precision", "get_float32_matmul_precision", "float32_matmul_precision", "DevicePairPool", "ProgressiveSchedule", "losses"]
+           "set_float32_matmul_precision", "get_float32_matmul_precision", "float32_matmul_precision", "DevicePairPool", "ProgressiveSchedule", "losses",
+           "degradations"]

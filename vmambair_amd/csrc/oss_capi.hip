@@ -816,6 +816,31 @@ int oss_niqe_features(oss_dtype io, const void *a, const double *tables, const d
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t oss_filter2d_workgroups(int64_t batch, int64_t channels, int64_t h, int64_t w, int k, int64_t kernels) {
+    return filter2d_workgroups(batch, channels, h, w, k, kernels);
+}
+int oss_filter2d(const float *img, const float *kernel, float *out, int64_t batch, int64_t channels, int64_t h, int64_t w, int k,
+                 int64_t kernels, int epilogue, oss_stream_t stream) {
+    if (!img || !kernel || !out) return OSS_ERR_NULL;
+    return filter2d(img, kernel, out, batch, channels, h, w, k, kernels, epilogue, reinterpret_cast<hipStream_t>(stream));
+}
+size_t oss_filter_sep_scratch_floats(int64_t batch, int64_t channels, int64_t h, int64_t w, int k) {
+    return filter_sep_scratch_floats(batch, channels, h, w, k);
+}
+int oss_filter_sep(const float *img, const float *g, float *out, float *scratch, int64_t batch, int64_t channels, int64_t h,
+                   int64_t w, int k, oss_stream_t stream) {
+    if (!img || !g || !out || !scratch) return OSS_ERR_NULL;
+    return filter_sep(img, g, out, scratch, batch, channels, h, w, k, reinterpret_cast<hipStream_t>(stream));
+}
+size_t oss_usm_scratch_floats(int64_t batch, int64_t channels, int64_t h, int64_t w, int k) {
+    return usm_scratch_floats(batch, channels, h, w, k);
+}
+int oss_usm_sharp(const float *img, const float *g, float *out, float *mask, float *scratch, int64_t batch, int64_t channels,
+                  int64_t h, int64_t w, int k, float weight, float threshold, oss_stream_t stream) {
+    if (!img || !g || !out || !scratch) return OSS_ERR_NULL;   // mask is optional
+    return usm_sharp(img, g, out, mask, scratch, batch, channels, h, w, k, weight, threshold, reinterpret_cast<hipStream_t>(stream));
+}
+
 size_t oss_pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t batch, int64_t channels,
                                       int64_t plane) {
     return pixel_loss_partial_doubles(kind, flags, pred_io, target_io, batch, channels, plane);

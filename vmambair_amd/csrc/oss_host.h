@@ -222,6 +222,16 @@ int image_metrics(oss_dtype io, const void *a, const void *b, double *out, doubl
 int niqe_features_ok(int C, int H, int W, int crop, int flags, oss_dtype io);
 int niqe_features(oss_dtype io, const void *a, const double *tables, const double *window, double *out, int B, int C, int H, int W,
                   int64_t asb, int64_t asc, int64_t ars, int crop, int flags, hipStream_t s);
+// filter2D and USM sharpening of the RealSR degradation pipeline (oss_degrade.hip); the size queries return 0 for a refused shape
+size_t filter2d_workgroups(int64_t B, int64_t C, int64_t H, int64_t W, int k, int64_t kernels);
+int filter2d(const float *img, const float *kernel, float *out, int64_t B, int64_t C, int64_t H, int64_t W, int k, int64_t kernels,
+             int epilogue, hipStream_t s);
+size_t filter_sep_scratch_floats(int64_t B, int64_t C, int64_t H, int64_t W, int k);
+int filter_sep(const float *img, const float *g, float *out, float *scratch, int64_t B, int64_t C, int64_t H, int64_t W, int k,
+               hipStream_t s);
+size_t usm_scratch_floats(int64_t B, int64_t C, int64_t H, int64_t W, int k);
+int usm_sharp(const float *img, const float *g, float *out, float *mask, float *scratch, int64_t B, int64_t C, int64_t H, int64_t W,
+              int k, float weight, float threshold, hipStream_t s);
 // pixel losses with their gradients (oss_pixel_loss.hip); N, C, plane = batch, channels, H * W
 size_t pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t N, int64_t C, int64_t plane);
 size_t pixel_loss_stat_doubles(int kind, int flags, int64_t N, int64_t C, int64_t plane);

@@ -1,0 +1,195 @@
+"""The custom operators of the RealSR degradation pipeline, which ``MambaRealSR.feed_data`` runs on the GPU under ``no_grad`` before
+every training step (RealSR/VmambaIR/models/MambaRealSR_model.py:146-263):
+
+  ``filter2D(img, kernel)``         a different 21 x 21 blur or sinc kernel per sample after reflect padding (:165, :196, :232/245)
+  ``USMSharp(radius=50, sigma=0)``  unsharp masking of the ground truth with a 51 x 51 Gaussian (:154-155, :262)
+  ``gaussian_kernel1d(k, sigma)``   the Gaussian vector ``USMSharp`` is built from
+  ``TrainingPairPool(queue_size)``  the training pair pool ``_dequeue_and_enqueue`` (:109-144)
+
+The reference imports ``filter2D`` and ``USMSharp`` from the pip ``basicsr`` package (``basicsr.utils``,
+``basicsr.utils.img_process_util``), which is not part of the reference tree.  Their definitions are restated here from that package's
+published source, and every test is anchored to an independent float64 evaluation of these formulas
+(``scipy.ndimage.correlate(..., mode='mirror')``, tests/golden/make_golden_degrade.py), not to reference code.  The pair pool is in the
+reference tree; its fixture is a trace of the reference's own method.
+
+fp32 device tensors go to the HIP kernels of ``csrc/oss_degrade.hip`` (``torch.ops.vmambair.filter2d`` / ``usm_sharp``):
+``filter2D`` for odd k <= 21, reflect addressing inside the load, with the ``clamp`` to [0, 1] (:190, :235, :240) or the final
+quantisation ``clamp((x * 255).round(), 0, 255) / 255`` (:248) as the kernel's last stage; ``USMSharp`` as four separable passes with
+the 51-vector it built itself (4 k taps per pixel where the dense form has 2 k^2).  Nothing in ``feed_data`` is differentiated, so no
+backward exists: the device paths run under ``torch.no_grad`` and return tensors without a graph.  A plain-torch restatement serves
+CPU tensors, non-fp32 input, k above the kernels' limits and, in ``filter2D``, a large (1, k, k) kernel, which need not be rank 1 -- as
+``losses.py`` and ``metrics.py`` do for CPU inputs.  ``DiffJPEG``, the other operator of ``feed_data`` that lives in ``basicsr``, is
+not here.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+from . import ops as _ops
+
+# OpenCV's getGaussianKernel uses these fixed vectors for sigma <= 0 and k <= 7
+_SMALL_GAUSSIAN = {1: (1.0,), 3: (0.25, 0.5, 0.25), 5: (0.0625, 0.25, 0.375, 0.25, 0.0625),
+                   7: (0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125)}
+
+
+# ---------------------------------------------------------------------------------------------
+# the restatement (dtype-preserving: on float64 inputs it is the formula in float64)
+# ---------------------------------------------------------------------------------------------
+def restate_filter2d(img: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
+    """basicsr.utils.img_process_util.filter2D: reflect pad, then a grouped cross-correlation (no kernel flip)"""
+    k = kernel.size(-1)
+    b, c, h, w = img.size()
+    if k % 2 == 1:
+        img = F.pad(img, (k // 2, k // 2, k // 2, k // 2), mode='reflect')
+    else:
+        raise ValueError('Wrong kernel size')
+    ph, pw = img.size()[-2:]
+    if kernel.size(0) == 1:
+        # one kernel for all samples
+        img = img.view(b * c, 1, ph, pw)
+        kernel = kernel.view(1, 1, k, k)
+        return F.conv2d(img, kernel, padding=0).view(b, c, h, w)
+    img = img.view(1, b * c, ph, pw)
+    kernel = kernel.view(b, 1, k, k).repeat(1, c, 1, 1).view(b * c, 1, k, k)
+    return F.conv2d(img, kernel, groups=b * c).view(b, c, h, w)
+
+
+def restate_quantise(x: torch.Tensor) -> torch.Tensor:
+    """MambaRealSR_model.py:248"""
+    return torch.clamp((x * 255.0).round(), 0, 255) / 255.
+
+
+def restate_usm(img: torch.Tensor, kernel: torch.Tensor, weight: float = 0.5, threshold: float = 10) -> torch.Tensor:
+    """basicsr.utils.img_process_util.USMSharp.forward"""
+    blur = restate_filter2d(img, kernel)
+    residual = img - blur
+    mask = (torch.abs(residual) * 255 > threshold).to(img.dtype)
+    soft_mask = restate_filter2d(mask, kernel)
+    sharp = torch.clip(img + weight * residual, 0, 1)
+    return soft_mask * sharp + (1 - soft_mask) * img
+
+
+# ---------------------------------------------------------------------------------------------
+# the public face
+# ---------------------------------------------------------------------------------------------
+def filter2D(img: torch.Tensor, kernel: torch.Tensor, *, clamp: bool = False, quantise: bool = False) -> torch.Tensor:
+    """``img`` (B, C, H, W) correlated with ``kernel`` (1, k, k), (B, k, k) or (k, k) after reflect padding by k // 2:
+    ``out[b,c,y,x] = sum_ij kernel[b or 0, i, j] * pad[b,c,y+i,x+j]``.  k must be odd (``ValueError('Wrong kernel size')``) and H, W
+    > k // 2 (torch's reflect pad raises otherwise).  ``clamp`` then clamps to [0, 1], ``quantise`` applies
+    ``clamp((x * 255).round(), 0, 255) / 255``; on the device both are the kernel's last stage, bit-equal to torch's expressions
+    there (torch divides a device tensor by 255 as a multiplication by fp32(1 / 255), the CPU path divides: one unit in the last place
+    apart at some levels, as the reference itself is between the two).  No gradient flows through the device path."""
+    if kernel.dim() == 2:
+        kernel = kernel.unsqueeze(0)
+    if kernel.dim() != 3 or kernel.size(-1) != kernel.size(-2) or img.dim() != 4 or kernel.size(0) not in (1, img.size(0)):
+        raise ValueError(f"filter2D: img must be (B, C, H, W) and kernel (k, k), (1, k, k) or (B, k, k): {tuple(img.shape)}, "
+                         f"{tuple(kernel.shape)}")
+    if kernel.size(-1) % 2 == 0:
+        raise ValueError('Wrong kernel size')
+    if img.is_cuda and kernel.device == img.device and img.dtype == kernel.dtype and _ops.filter2d_ok(img, kernel):
+        with torch.no_grad():
+            return _ops.filter2d(img.contiguous(), kernel.contiguous(),
+                                 _ops.degrade.QUANTISE if quantise else _ops.degrade.CLAMP if clamp else _ops.degrade.NONE)
+    out = restate_filter2d(img, kernel)
+    if clamp:
+        out = torch.clamp(out, 0, 1)
+    return restate_quantise(out) if quantise else out
+
+
+def gaussian_kernel1d(k: int, sigma: float = 0) -> torch.Tensor:
+    """cv2.getGaussianKernel(k, sigma) as a float64 vector: ``g_i ~ exp(-(i - (k - 1) / 2)^2 / (2 sigma^2))`` normalised to sum 1;
+    ``sigma <= 0`` stands for ``0.3 * ((k - 1) * 0.5 - 1) + 0.8`` (OpenCV's fixed vectors for k <= 7 in that case)."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"gaussian_kernel1d: k must be positive, not {k}")
+    if sigma <= 0 and k % 2 == 1 and k in _SMALL_GAUSSIAN:
+        return torch.tensor(_SMALL_GAUSSIAN[k], dtype=torch.float64)
+    s = float(sigma) if sigma > 0 else 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    x = torch.arange(k, dtype=torch.float64) - (k - 1) * 0.5
+    g = torch.exp(x * x * (-0.5 / (s * s)))
+    return g * (1.0 / g.sum())
+
+
+class USMSharp(nn.Module):
+    """basicsr.utils.img_process_util.USMSharp: the buffer ``kernel`` is float32(g g^T), shape (1, k, k), k = ``radius`` made odd
+    (51), so a reference ``state_dict`` loads.  ``forward(img, weight=0.5, threshold=10)``::
+
+        blur = filter2D(img, kernel); residual = img - blur; mask = (|residual| * 255 > threshold)
+        soft = filter2D(mask, kernel); sharp = clip(img + weight * residual, 0, 1)
+        return soft * sharp + (1 - soft) * img
+
+    fp32 device tensors run as four separable passes with ``g`` (``torch.ops.vmambair.usm_sharp``, no gradient); everything else, and
+    a module whose ``kernel`` was loaded with other values than g g^T, uses the restatement with ``self.kernel``."""
+
+    def __init__(self, radius: int = 50, sigma: float = 0):
+        super().__init__()
+        if radius % 2 == 0:
+            radius += 1
+        self.radius = radius
+        g = gaussian_kernel1d(radius, sigma)
+        self.register_buffer('kernel', torch.outer(g, g).float().unsqueeze_(0))
+        self.register_buffer('_g', g.float(), persistent=False)
+        self._separable = True
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        # a kernel made elsewhere (cv2 in the reference) differs from ours in the last bits only; anything else is another kernel
+        g = self._g.double().to(self.kernel.device)
+        self._separable = bool(torch.allclose(self.kernel.double(), torch.outer(g, g).unsqueeze(0), rtol=1e-5, atol=1e-10))
+
+    def forward(self, img: torch.Tensor, weight: float = 0.5, threshold: float = 10) -> torch.Tensor:
+        on_device = img.is_cuda and self._g.device == img.device and self._g.dtype == torch.float32
+        if self._separable and on_device and _ops.filter_sep_ok(img, self.radius):
+            with torch.no_grad():
+                return _ops.usm_sharp(img.contiguous(), self._g, float(weight), float(threshold), False)[0]
+        return restate_usm(img, self.kernel, weight, threshold)
+
+
+class TrainingPairPool:
+    """``MambaRealSR._dequeue_and_enqueue`` (MambaRealSR_model.py:109-144): a pool of ``queue_size`` (lq, gt) pairs that mixes the
+    degradations of several batches into one.  ``push_pop(lq, gt)`` while the pool fills only stores the batch and returns it
+    unchanged; once full it draws ``idx = torch.randperm(queue_size)`` (the CPU default generator, exactly where the reference draws
+    it, so the same seed gives the same stream), reorders the pool by ``idx``, hands out its first b pairs and puts the new batch in
+    their place.  ``queue_size % b == 0`` is asserted at the first call.
+
+    The reference copies the whole pool (``queue[idx]``, about 2 x 150 MB per step at queue 180) to reorder it; here the order is a
+    slot permutation on the host and only the b pairs that leave and the b that enter move.  ``queue()`` gives the pool in the
+    reference's order."""
+
+    def __init__(self, queue_size: int):
+        self.queue_size = int(queue_size)
+        self.queue_lr: Optional[torch.Tensor] = None
+        self.queue_gt: Optional[torch.Tensor] = None
+        self.queue_ptr = 0
+        self.slots = torch.arange(self.queue_size)   # position in the reference's queue -> row of queue_lr / queue_gt
+
+    @torch.no_grad()
+    def push_pop(self, lq: torch.Tensor, gt: torch.Tensor, perm: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        b, c, h, w = lq.size()
+        if self.queue_lr is None:
+            assert self.queue_size % b == 0, f'queue size {self.queue_size} should be divisible by batch size {b}'
+            self.queue_lr = torch.zeros(self.queue_size, c, h, w, dtype=lq.dtype, device=lq.device)
+            _, c, h, w = gt.size()
+            self.queue_gt = torch.zeros(self.queue_size, c, h, w, dtype=gt.dtype, device=gt.device)
+            self.queue_ptr = 0
+        if self.queue_ptr == self.queue_size:   # the pool is full: shuffle, dequeue the first b, enqueue the batch there
+            idx = torch.randperm(self.queue_size) if perm is None else torch.as_tensor(perm, dtype=torch.long, device='cpu')
+            self.slots = self.slots[idx]
+            rows = self.slots[:b].to(lq.device)
+            lq_out, gt_out = self.queue_lr.index_select(0, rows), self.queue_gt.index_select(0, rows)
+            self.queue_lr.index_copy_(0, rows, lq)
+            self.queue_gt.index_copy_(0, rows, gt)
+            return lq_out, gt_out
+        self.queue_lr[self.queue_ptr:self.queue_ptr + b] = lq   # only enqueue
+        self.queue_gt[self.queue_ptr:self.queue_ptr + b] = gt
+        self.queue_ptr += b
+        return lq, gt
+
+    def queue(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the pool in the reference's order (``queue_lr``, ``queue_gt`` of the reference after the same calls)"""
+        rows = self.slots.to(self.queue_lr.device)
+        return self.queue_lr.index_select(0, rows), self.queue_gt.index_select(0, rows)
