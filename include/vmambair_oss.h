@@ -207,6 +207,30 @@ int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream
 size_t oss_scan_bwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, int n_groups);
 int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream);
 
+/* What a call would launch, without launching it: oss_scan_fwd_describe / oss_scan_bwd_describe fill `out` with the plan that
+ * oss_scan_fwd / oss_scan_bwd run for the same block, element type and test overrides.  Pure host arithmetic on the block's
+ * integers and on which of its pointers are NULL (workspace, hs, dt_weight, dD, ddelta_bias, ddt, ddt_weight): the data pointers
+ * are neither required nor read, only the shape rules of the entry points apply (same OSS_ERR_* codes, plus OSS_ERR_WORKSPACE
+ * from the backward when no launch fits workspace_bytes).  An empty call (batch or seqlen 0) gives OSS_OK, variant -1, zeros. */
+typedef struct {
+    int variant;             /* the selected variant number: what oss_scan_last_variant reports after the call */
+    int rows_per_workgroup;  /* of the kernel that runs (a variant that does not fit this shape runs another variant's kernel) */
+    int chunk;               /* its time steps per chunk */
+    int workgroups;          /* batch x groups x row tiles; a time-segmented launch runs workgroups x segments */
+    int segments;            /* time segments per row: what oss_scan_last_segments reports (1 = unsegmented) */
+    int chunks_per_segment;  /* the last segment may be shorter */
+    int carry_pieces;        /* pieces per segment of the local / reverse-carry pass (oss_scan_set_carry_split) */
+    int chunks_per_piece;    /* ceil(chunks_per_segment / carry_pieces); segments x carry_pieces carry slots per row */
+    int lane_states;         /* backward: 1 = the kernels that load f.hs (oss_scan_last_lane_states) */
+    int fused_delta;         /* 1 = delta evaluated inside the scan (dt_weight) */
+    int bf16_partials;       /* backward: 1 = bf16 row-tile partials (tune_partials == 2 honoured) */
+    int reserved_;
+    size_t lds_bytes;        /* dynamic LDS per workgroup of the main kernel */
+    size_t workspace_bytes;  /* of the caller's workspace this launch uses (<= the oss_scan_*_workspace_bytes query) */
+} oss_scan_launch;
+int oss_scan_fwd_describe(const oss_scan_fwd_params *p, oss_dtype io, oss_scan_launch *out);
+int oss_scan_bwd_describe(const oss_scan_bwd_params *p, oss_dtype io, oss_scan_launch *out);
+
 /* 1 when oss_scan_bwd_params.finish_dt_weight may be used at this length / rank (see the struct) */
 int oss_scan_bwd_finish_dt_ok(int seqlen, int dt_rank);
 

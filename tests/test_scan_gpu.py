@@ -8,6 +8,7 @@ others ``randn``, seed 0 -- with ``dstate = 16`` (the only value the archs use) 
 reference's ``dstate = 1``, odd / multi-chunk lengths, strided B/C views and ragged row tiles.
 Tolerances are the reference's (:398-401,490-502) and are written next to each comparison.
 """
+import ctypes
 import itertools
 
 import pytest
@@ -1106,3 +1107,97 @@ def test_shipped_library_has_both_runtime_selected_scan_forms():
     assert lib.oss_scan_lane_state_floats(1, 8, 700, 16) > 0
     assert lib.oss_scan_fused_dt_ok(_capi.OSS_BF16, 8, 96, 38, 6, 16, 4096) == 1
     assert lib.oss_scan_fused_dt_ok(_capi.OSS_BF16, 8, 384, 56, 24, 16, 4096) == 0      # dt_rank > 8 stays on the materialised delta
+
+
+# ------------------------------------------------------------------------------------------------
+# the host plan (csrc/oss_scan_plan.h): what oss_scan_*_describe says is what the launchers ran
+# ------------------------------------------------------------------------------------------------
+_IO = {torch.float32: _capi.OSS_F32, torch.float16: _capi.OSS_F16, torch.bfloat16: _capi.OSS_BF16}
+
+
+def _described(which, batch, dim, N, G, L, itype, tune=None, hs=False, dt_rank=0):
+    """oss_scan_fwd_describe (which = 0) / oss_scan_bwd_describe (1) of the block the compiled boundary fills for such a call: the
+    shape, a workspace of the queried size, the tune fields and the presence of dt_weight / hs (stand-in addresses: never read)"""
+    from vmambair_amd.ops.scan import _tune_fields
+    lib = _capi.load()
+    tv, ts, tc, tp = _tune_fields(tune)
+    q = _capi.ScanBwdParams()
+    p = q.f
+    p.batch, p.dim, p.seqlen, p.dstate, p.n_groups, p.rev_group_start = batch, dim, L, N, G, G
+    p.tune_carry_split = tc
+    if dt_rank:
+        p.dt_weight, p.dt_rank, q.ddt, q.ddt_weight = 64, dt_rank, 64, 64
+    o = _capi._HDR.structs["oss_scan_launch"]()
+    if which == 0:
+        p.tune_variant, p.tune_segments = tv, ts
+        p.workspace_bytes = lib.oss_scan_fwd_workspace_bytes(batch, dim, L, N, G)
+        p.workspace = 64 if p.workspace_bytes else None
+        rc = lib.oss_scan_fwd_describe(ctypes.byref(p), _IO[itype], ctypes.byref(o))
+    else:
+        q.tune_variant, q.tune_segments, q.tune_partials = tv, ts, tp
+        p.hs = 64 if hs else None
+        q.workspace, q.workspace_bytes = 64, max(16, lib.oss_scan_bwd_workspace_bytes(batch, dim, L, N, G))
+        rc = lib.oss_scan_bwd_describe(ctypes.byref(q), _IO[itype], ctypes.byref(o))
+    assert rc == 0
+    return o
+
+
+def test_described_launch_is_the_launch_that_ran():
+    """about a dozen small calls: forced segments on every backward variant, the large-dstate remap, lane states, the fused-delta
+    form and bf16 partials -- after each, oss_scan_last_variant / _segments / _lane_states equal the described launch"""
+    lib = _capi.load()
+
+    def ran(which):
+        return (lib.oss_scan_last_variant(which), lib.oss_scan_last_segments(which), lib.oss_scan_last_lane_states() if which else 0)
+
+    def said(o):
+        return (o.variant, o.segments, o.lane_states)
+
+    def both(shape, itype, tune_f=None, tune_b=None, hs=False):
+        batch, dim, N, G, L = shape
+        u, delta, A, B, C, D, bias, dout = to_dev(make_inputs(*shape, itype))
+        res = vmambair_amd.selective_scan_fwd(u, delta, A, B, C, D, bias, True, 1, want_hs=hs, tune=tune_f)
+        f = _described(0, batch, dim, N, G, L, itype, tune_f)
+        assert ran(0) == said(f)
+        vmambair_amd.selective_scan_bwd(u, delta, A, B, C, D, bias, dout, res[1], True, 1, hs=res[2] if hs else None, tune=tune_b)
+        b = _described(1, batch, dim, N, G, L, itype, tune_b, hs=hs)
+        assert ran(1) == said(b)
+        return f, b
+
+    try:
+        for segs, bv in itertools.product((3, 4), (1, 10, 11, 12, 13)):
+            lib.oss_scan_set_segments(segs, segs)
+            lib.oss_scan_set_variant(-1, bv)
+            f, b = both((2, 26, 16, 2, 3000), torch.float32)
+            # 3000 steps are 3 chunks of 1024 (forward) and 6 of 512 (round-2 backward): both requests round to 3 segments of whole chunks
+            assert f.chunk == 1024 and f.segments == 3 and b.segments == (3 if bv >= 10 else 1)
+        lib.oss_scan_set_segments(-1, -1)
+        lib.oss_scan_set_variant(-1, -1)
+        f, b = both((1, 8, 72, 2, 1500), torch.float32, tune_b=(11, 2, None))      # dstate > 64: the round-1 kernel, never cut
+        assert (b.variant, b.rows_per_workgroup, b.chunk, b.segments) == (11, 4, 256, 1)
+        f, b = both((2, 24, 16, 2, 2085), torch.bfloat16, hs=True)
+        assert b.lane_states == 1
+        f, b = both((2, 24, 16, 2, 2085), torch.bfloat16, tune_b=(10, 1, None, "bf16"))
+        assert b.bf16_partials == 1 and b.segments == 1
+        # the fused-delta form as SS2D_1 issues it (test_fused_delta_scan_matches_materialised_delta): variant 13, never cut
+        _need_feature(_capi.FEATURE_FUSED_DT, "fused_dt")
+        K, N, Bsz, rows, R, L = 4, 16, 2, 24, 5, 700
+        g = torch.Generator().manual_seed(5)
+        x2 = torch.randn(Bsz, 2 * rows, L, generator=g).to(DEV)
+        xdbl = torch.randn(Bsz, K, R + 2 * N, L, generator=g).to(DEV)
+        W = (torch.randn(K * rows, R, generator=g) * 0.5).to(DEV)
+        A_log = torch.log(0.5 + torch.rand(K * rows, N, generator=g)).to(DEV)
+        dout = torch.randn(Bsz, 2 * rows, L, generator=g).to(DEV)
+        kw = dict(rev_group_start=2, u_row_mod=2 * rows, a_log_form=True, dt_weight=W)
+        lib.oss_scan_set_segments(2, 2)
+        out, x = vmambair_amd.selective_scan_fwd(x2, xdbl, A_log, xdbl[:, :, R:R + N], xdbl[:, :, R + N:], None, None, True, 1, **kw)
+        f = _described(0, Bsz, K * rows, N, K, L, torch.float32, dt_rank=R)
+        assert ran(0) == said(f) and f.fused_delta == 1 and f.segments == 1
+        vmambair_amd.selective_scan_bwd(x2, xdbl, A_log, xdbl[:, :, R:R + N], xdbl[:, :, R + N:], None, None, dout, x, True, 1,
+                                        dout_row_mod=2 * rows, dbc_into=torch.empty_like(xdbl), tune=(13, None, None), **kw)
+        b = _described(1, Bsz, K * rows, N, K, L, torch.float32, (13, None, None), dt_rank=R)
+        assert ran(1) == said(b) and (b.fused_delta, b.segments, b.rows_per_workgroup) == (1, 1, 4)
+        torch.cuda.synchronize()
+    finally:
+        lib.oss_scan_set_segments(-1, -1)
+        lib.oss_scan_set_variant(-1, -1)

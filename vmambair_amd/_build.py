@@ -21,7 +21,7 @@ HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "vmambair_oss.h"))
 
 
 #: the files the scan kernels are compiled from: their hash is the library's oss_scan_build_id()
-SCAN_FILES = ("oss_scan_fwd.hip", "oss_scan_bwd.hip", "oss_scan_bwd_v2.h", "oss_device.h")
+SCAN_FILES = ("oss_scan_fwd.hip", "oss_scan_bwd.hip", "oss_scan_bwd_v2.h", "oss_device.h", "oss_scan_plan.h")
 
 
 def scan_build_id() -> str:

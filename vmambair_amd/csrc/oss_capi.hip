@@ -9,49 +9,12 @@
 
 namespace oss {
 
+// test-only overrides (oss_scan_set_variant / _segments; -1 = heuristic) and what the last call ran (oss_scan_last_*)
 static std::atomic<int> g_force_fwd{-1}, g_force_bwd{-1};
-static std::atomic<int> g_last_fwd{-1}, g_last_bwd{-1};
 static std::atomic<int> g_force_fwd_seg{-1}, g_force_bwd_seg{-1};
-std::atomic<int> g_last_fwd_segments{1}, g_last_bwd_segments{1}, g_last_bwd_lane_states{0};
+static std::atomic<int> g_last_fwd{-1}, g_last_bwd{-1};
+static std::atomic<int> g_last_fwd_segments{1}, g_last_bwd_segments{1}, g_last_bwd_lane_states{0};
 
-// Segments of a launch that has `wgs` workgroups (one per CU at a time for the wide variants) over `n_chunks` chunks when
-// it is not cut in time.  Cost model in units of one chunk of one workgroup: rounds over the 256 CUs x chunks per segment x
-// (1 + ovh), where ovh is the extra sweep a segmented launch pays (forward: the B side of the step again, ~0.55 of a pass;
-// backward: the reverse recurrence alone, ~0.3).  Launches that already put a workgroup on every CU are left alone, and a
-// larger segment count has to win by 5 % to be taken.
-int scan_pick_segments(long wgs, int n_chunks, int seg_req, double ovh) {
-    if (seg_req == 0 || seg_req == 1 || n_chunks < 2 || wgs <= 0) return 1;
-    if (seg_req > 1) return std::min(std::min(seg_req, n_chunks), kMaxSegments);
-    if (wgs >= 256) return 1;
-    int best = 1;
-    double best_cost = (double)n_chunks;
-    for (int s = 2; s <= std::min(n_chunks, 16); ++s) {
-        const int cps = (n_chunks + s - 1) / s;
-        if ((n_chunks + cps - 1) / cps != s) continue;   // not a segment count this chunk count can have
-        const double rounds = (double)((wgs * s + 255) / 256);
-        const double cost = rounds * cps * (1.0 + ovh);
-        if (cost < 0.95 * best_cost) { best = s; best_cost = cost; }
-    }
-    return best;
-}
-
-static std::atomic<int> g_carry_split{0};
-int scan_carry_split(long wgs, int n_seg, int cps, int n_chunks, int per_call) {
-    if (n_seg <= 1) return 1;
-    const int forced = per_call > 0 ? per_call : g_carry_split.load();   // the call's own field wins over the test-only global
-    const int max_slots = std::min(n_chunks, kMaxSegments);   // what the workspace queries size the carry area for
-    int csub = 1;
-    for (int c = 2; c <= cps; ++c) {
-        const int ccps = (cps + c - 1) / c, pieces = (cps + ccps - 1) / ccps;   // pieces of ccps chunks, the last one shorter
-        if (n_seg * pieces > max_slots) break;
-        if (forced > 0 ? pieces <= forced : wgs * (n_seg - 1) * pieces <= 512) csub = pieces;
-    }
-    return csub;
-}
-
-// ---- variant heuristics -----------------------------------------------------------------------
-// The forward/backward kernels are VALU-bound, so the cheapest variant in instructions per
-// (element, state) wins as long as the launch still fills 256 CUs x 4 SIMDs with >= 2 waves.
 static std::atomic<int> g_defer_finish{0};
 static std::mutex g_defer_mu;
 static std::vector<oss_sum_chunk> g_defer_chunks;
@@ -82,52 +45,6 @@ void defer_wgrad_push(const void *desc, size_t bytes, unsigned blocks) {
     g_wgrad_blocks.push_back(blocks);
 }
 
-int scan_fwd_pick_variant(int batch, int dim, int seqlen, int dstate, int n_groups, int elem_bytes) {
-    (void)dstate; (void)elem_bytes;
-    const int rows_per_group = dim / n_groups;
-    const long rows = (long)batch * dim;
-    if (seqlen <= 256 || rows_per_group < 8) return (rows_per_group >= 16 && rows >= 4096) ? 2 : 4;
-    // 16 lanes per row (4 rows per wave): fewest scan steps, but only rows/4 waves
-    if (rows_per_group % 16 == 0 && rows / 4 >= 2048) return 2;
-    if (rows_per_group % 16 == 0 && rows / 2 >= 2048) return 1;
-    // long sequences whose 12-row tiles leave CUs idle (RealSR tiles at batch 1: u:(1,384,25600) is 32 workgroups; Deraining
-    // level 0 at batch 4: 64): the widest workgroup, cut into time segments by scan_pick_segments until the CUs are covered
-    // (u:(1,384,25600) f16 0.129 ms in 9 segments against 0.354 ms for one 8-row workgroup per tile; u:(4,192,16384) bf16
-    // 0.139 in 4 segments against 0.222 -- profiles/r03_segment_sweep.txt)
-    // (u:(1,768,6400) f16: 0.070 ms in 4 segments against 0.093.  At exactly 128 such workgroups -- u:(8,192,4096), u:(4,384,4096) --
-    // variant 3 stayed ahead until round 5; with the local pass cut finer than the main launch (oss_scan_set_carry_split) two
-    // segments of the 12-row form win there too: u:(4,384,4096) bf16 0.059 against 0.064 ms, profiles/r05_sweep_batch4_scan_variants_and_segments.txt)
-    if (seqlen >= 4096 && rows_per_group % 12 == 0 && (long)batch * n_groups * (rows_per_group / 12) <= 128) return 6;
-    // <= one 8-row workgroup per CU and a long sequence: 16 items per lane (half the chunk hand-overs; u:(8,192,4096)
-    // bf16 0.065 ms against 0.077, profiles/r01_sweep_v4_bwd_variants.txt)
-    if (seqlen >= 1024 && (long)batch * n_groups * ((rows_per_group + 7) / 8) <= 256) return 3;
-    // 12-row workgroups when they give <= one workgroup per CU (u:(8,384,4096) bf16: 0.081 ms against 0.113)
-    if (seqlen >= 1024 && rows_per_group >= 12 && (long)batch * n_groups * ((rows_per_group + 11) / 12) <= 256) return 6;
-    return 0;
-}
-
-int scan_bwd_pick_variant(int batch, int dim, int seqlen, int dstate, int n_groups) {
-    const int rows_per_group = dim / n_groups;
-    // short sequences, few rows per group, dstate > 64 (the round-2 kernel keeps one lane per state): the round-1 kernel
-    if (seqlen <= 256 || rows_per_group < 8 || dstate > 64) return 1;
-    const long wgs = (long)batch * n_groups * ((rows_per_group + 7) / 8);
-    // round-2 kernel (oss_scan_bwd_v2.h) from here on: u:(8,192,4096) 0.172 ms against 0.203 for the round-1 kernel,
-    // u:(8,384,4096) 0.235 against 0.284 (profiles/r02_scan_bwd_v2_experiments.txt)
-    // long sequences whose 12-row tiles leave CUs idle: 12-row workgroups cut into time segments (scan_pick_segments) instead
-    // of ever smaller row tiles -- a third of the dB / dC partial tiles of the 4-row form and three waves per SIMD
-    // (u:(4,192,16384) bf16: 0.328 + 0.029 ms in 4 segments against 0.590 + 0.087 for variant 13; u:(1,384,25600) f16:
-    // 0.293 + 0.022 in 9 segments against 1.316 -- profiles/r03_segment_sweep.txt)
-    // (u:(8,192,4096) bf16, 128 such workgroups: 0.166 + 0.015 ms in 2 segments against 0.168 + 0.020 for variant 11)
-    if (seqlen >= 2048 && rows_per_group % 12 == 0 && (long)batch * n_groups * (rows_per_group / 12) < 192) return 10;
-    // very few rows (Deraining level 0 at batch 4: 96 8-row workgroups for 256 CUs): 4-row workgroups spread the same waves over
-    // twice the CUs, one wave per SIMD instead of two (u:(4,192,16384): 0.585 ms against 0.684)
-    if (wgs <= 128 && rows_per_group % 4 == 0) return 13;
-    if (wgs <= 256) return 11;
-    // more rows per workgroup: fewer dB / dC partial tiles and an even load (u:(8,384,4096) bf16: 0.271 ms against
-    // 0.355; u:(32,384,4096): 1.07 against 1.14)
-    return rows_per_group >= 12 ? 10 : 11;
-}
-
 // ---- per-launch event timing (oss_prof_*) -----------------------------------------------------
 constexpr int kProfVariants = 32;   // 0..15: the kernel variants; 16 + v: time-segmented launches of variant v
 struct ProfBucket {
@@ -150,7 +67,7 @@ struct ProfTimer : LaunchTimer {  // begin/end bracket exactly one kernel launch
     ProfTimer(int which_, int variant_, int io_, double bytes_, double own_ = 0.0)
         : on(g_prof_on.load() != 0 && variant_ >= 0 && variant_ < 16), which(which_), variant(variant_),
           io(io_), bytes(bytes_), own(own_) {}
-    void segmented() override { if (variant < 16) variant += 16; }
+    void segmented() { if (variant < 16) variant += 16; }   // a time-segmented launch: its own bucket
     void begin(hipStream_t s) override {
         if (!on) return;
         {
@@ -241,14 +158,52 @@ static double bwd_own_bytes(const oss_scan_bwd_params &q, int s) {
     return v;
 }
 
-static int check_fwd(const oss_scan_fwd_params *p) {
-    if (!p || !p->u || !p->delta || !p->A || !p->B || !p->C) return OSS_ERR_NULL;
+// the shape rules of a scan block (what oss_scan_*_describe applies), and with them the data pointers of a call
+static int check_fwd_shape(const oss_scan_fwd_params *p) {
+    if (!p) return OSS_ERR_NULL;
     if (p->dt_weight && (p->dt_rank < 1 || p->dt_rank > kMaxDtRank)) return OSS_ERR_SHAPE;
     if (p->batch < 0 || p->dim <= 0 || p->seqlen < 0 || p->dstate <= 0 || p->n_groups <= 0) return OSS_ERR_SHAPE;
     if (p->dim % p->n_groups != 0) return OSS_ERR_SHAPE;  // selective_scan.cpp:190
     if (p->dstate > OSS_MAX_DSTATE) return OSS_ERR_DSTATE;  // selective_scan.cpp:191
     if (p->rev_group_start < 0 || p->u_row_mod < 0 || (p->u_row_mod > 0 && p->dim % p->u_row_mod != 0)) return OSS_ERR_SHAPE;
     return OSS_OK;
+}
+static int check_bwd_shape(const oss_scan_bwd_params *p) {
+    if (!p) return OSS_ERR_NULL;
+    if (const int rc = check_fwd_shape(&p->f)) return rc;
+    if (p->dout_row_mod < 0 || (p->dout_row_mod > 0 && p->f.dim % p->dout_row_mod != 0)) return OSS_ERR_SHAPE;
+    return OSS_OK;
+}
+static int check_fwd(const oss_scan_fwd_params *p) {
+    if (!p || !p->u || !p->delta || !p->A || !p->B || !p->C) return OSS_ERR_NULL;
+    return check_fwd_shape(p);
+}
+
+// The plan of a call: per-call fields (oss_scan_*_params.tune_*) win over the process-global test overrides; 0 / -1 = heuristic.
+// v: the selected variant number (oss_scan_last_variant), before the plan's remaps
+static int plan_fwd(const oss_scan_fwd_params &p, oss_dtype io, int &v, ScanFwdPlan &pl) {
+    v = p.tune_variant > 0 ? p.tune_variant - 1 : g_force_fwd.load();
+    if (v < 0) v = scan_fwd_pick_variant(p.batch, p.dim, p.seqlen, p.dstate, p.n_groups, io_bytes(io));
+    return scan_fwd_plan(p, io, v, p.tune_segments > 0 ? p.tune_segments : g_force_fwd_seg.load(), pl);
+}
+static int plan_bwd(const oss_scan_bwd_params &p, oss_dtype io, int &v, ScanBwdPlan &pl) {
+    v = p.tune_variant > 0 ? p.tune_variant - 1 : g_force_bwd.load();
+    if (v < 0) v = scan_bwd_pick_variant(p.f.batch, p.f.dim, p.f.seqlen, p.f.dstate, p.f.n_groups);
+    return scan_bwd_plan(p, io, v, p.tune_segments > 0 ? p.tune_segments : g_force_bwd_seg.load(), pl);
+}
+template <typename Plan>
+static void describe(oss_scan_launch *out, int v, const Plan &pl, bool lane_states, bool bf16_partials, size_t need_bytes) {
+    out->variant = v;
+    out->workgroups = (int)pl.wgs;
+    out->segments = pl.seg.n_seg;
+    out->chunks_per_segment = pl.seg.cps;
+    out->carry_pieces = pl.seg.csub;
+    out->chunks_per_piece = pl.seg.ccps;
+    out->lane_states = lane_states;
+    out->fused_delta = pl.fused_delta;
+    out->bf16_partials = bf16_partials;
+    out->lds_bytes = pl.lds_bytes;
+    out->workspace_bytes = need_bytes;
 }
 
 }  // namespace oss
@@ -260,6 +215,38 @@ extern "C" {
 int oss_scan_chunk(void) { return kScanChunk; }
 int oss_scan_num_chunks(int seqlen) { return seqlen <= 0 ? 0 : (seqlen + kScanChunk - 1) / kScanChunk; }
 
+int oss_scan_fwd_describe(const oss_scan_fwd_params *p, oss_dtype io, oss_scan_launch *out) {
+    if (!out) return OSS_ERR_NULL;
+    *out = oss_scan_launch{};
+    out->variant = -1;
+    if (!io_bytes(io)) return OSS_ERR_SHAPE;
+    if (const int rc = check_fwd_shape(p)) return rc;
+    if (p->batch == 0 || p->seqlen == 0) return OSS_OK;   // an empty call launches nothing
+    int v;
+    ScanFwdPlan pl;
+    if (const int rc = plan_fwd(*p, io, v, pl)) return rc;
+    describe(out, v, pl, false, false, pl.need_bytes);
+    out->rows_per_workgroup = pl.kernel.rows();
+    out->chunk = pl.kernel.chunk();
+    return OSS_OK;
+}
+
+int oss_scan_bwd_describe(const oss_scan_bwd_params *p, oss_dtype io, oss_scan_launch *out) {
+    if (!out) return OSS_ERR_NULL;
+    *out = oss_scan_launch{};
+    out->variant = -1;
+    if (!io_bytes(io)) return OSS_ERR_SHAPE;
+    if (const int rc = check_bwd_shape(p)) return rc;
+    if (p->f.batch == 0 || p->f.seqlen == 0) return OSS_OK;
+    int v;
+    ScanBwdPlan pl;
+    if (const int rc = plan_bwd(*p, io, v, pl)) return rc;
+    describe(out, v, pl, pl.lane_states, pl.bf16_partials, pl.ws.need_bytes);
+    out->rows_per_workgroup = pl.kernel.rows;
+    out->chunk = pl.kernel.chunk;
+    return OSS_OK;
+}
+
 int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream) {
     const int eb = io_bytes(io);
     if (!eb) return OSS_ERR_SHAPE;
@@ -267,40 +254,23 @@ int oss_scan_fwd(const oss_scan_fwd_params *p, oss_dtype io, oss_stream_t stream
     if (rc != OSS_OK) return rc;
     if (!p->out || !p->x) return OSS_ERR_NULL;
     if (p->batch == 0 || p->seqlen == 0) return OSS_OK;
-    // per-call fields (oss_scan_fwd_params.tune_*) win over the process-global test overrides; 0 / -1 = heuristic
-    int v = p->tune_variant > 0 ? p->tune_variant - 1 : g_force_fwd.load();
-    if (v < 0) v = scan_fwd_pick_variant(p->batch, p->dim, p->seqlen, p->dstate, p->n_groups, eb);
+    int v;
+    ScanFwdPlan pl;
+    rc = plan_fwd(*p, io, v, pl);
     g_last_fwd.store(v);
-    g_last_fwd_segments.store(1);
-    const int sr = p->tune_segments > 0 ? p->tune_segments : g_force_fwd_seg.load();
+    g_last_fwd_segments.store(rc == OSS_OK ? pl.seg.n_seg : 1);
+    if (rc != OSS_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfTimer prof(0, v, (int)io, fwd_alg_bytes(*p, eb), fwd_own_bytes(*p, eb));
+    if (pl.seg.n_seg > 1) prof.segmented();   // local pass + real pass: timed as one call
     prof.begin(s);
-    rc = io_dispatch(io, [&](auto tag) { return scan_fwd_dispatch<typename decltype(tag)::type>(*p, v, sr, s); });
-    if (g_last_fwd_segments.load() > 1) prof.segmented();   // local pass + real pass: timed as one call, in its own bucket
+    rc = io_dispatch(io, [&](auto tag) { return scan_fwd_dispatch<typename decltype(tag)::type>(*p, pl, s); });
     prof.end(s);
     return rc;
 }
 
-static int bwd_variant_for(int batch, int dim, int seqlen, int dstate, int n_groups, int per_call = 0) {
-    int v = per_call > 0 ? per_call - 1 : g_force_bwd.load();
-    if (v < 0) v = scan_bwd_pick_variant(batch, dim, seqlen, dstate, n_groups);
-    return v;
-}
-
 size_t oss_scan_bwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, int n_groups) {
-    if (batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0 || n_groups <= 0 || dim % n_groups) return 0;
-    // sized for the variant with the fewest rows per workgroup so that any variant fits
-    const int rows_per_group = dim / n_groups;
-    const int rows = scan_bwd_rows_per_wg(1);
-    const size_t tiles = (size_t)(rows_per_group + rows - 1) / rows;
-    // + kMaxDtRank partial rows per tile and kMaxDtRank dt-weight partials per (batch, row): the fused-delta form;
-    // time-segmented launches: one weight-gradient partial per (batch, segment, row) + the reverse-carry pairs
-    const size_t segs = (size_t)std::min(kMaxSegments, std::max(1, (seqlen + 511) / 512));
-    const size_t floats = (size_t)batch * n_groups * tiles * (2 * dstate + kMaxDtRank) * seqlen +
-                          (size_t)batch * segs * dim * (dstate + 2 + kMaxDtRank) +
-                          (segs > 1 ? 2 * (size_t)batch * dim * dstate * segs : 0);
-    return floats * sizeof(float);
+    return scan_bwd_workspace_bytes(batch, dim, seqlen, dstate, n_groups);
 }
 
 size_t oss_scan_lane_state_floats(int batch, int dim, int seqlen, int dstate) {
@@ -309,9 +279,7 @@ size_t oss_scan_lane_state_floats(int batch, int dim, int seqlen, int dstate) {
 }
 
 size_t oss_scan_fwd_workspace_bytes(int batch, int dim, int seqlen, int dstate, int n_groups) {
-    if (batch <= 0 || dim <= 0 || seqlen <= 0 || dstate <= 0 || n_groups <= 0 || dim % n_groups) return 0;
-    const int segs = std::min(kMaxSegments, (seqlen + kScanChunk - 1) / kScanChunk);   // the shortest chunk any variant has
-    return segs > 1 ? scan_carry_bytes(batch, dim, dstate, segs) : 0;
+    return scan_fwd_workspace_bytes(batch, dim, seqlen, dstate, n_groups);
 }
 
 int oss_scan_bwd_finish_dt_ok(int seqlen, int dt_rank) { return scan_finish_dt_ok(seqlen, dt_rank) ? 1 : 0; }
@@ -328,15 +296,20 @@ int oss_scan_bwd(const oss_scan_bwd_params *p, oss_dtype io, oss_stream_t stream
     const oss_scan_fwd_params &f = p->f;
     if (f.batch == 0 || f.seqlen == 0) return OSS_OK;
     if (!f.x && oss_scan_num_chunks(f.seqlen) > 1) return OSS_ERR_NULL;  // selective_scan.cpp:310
-    if (p->dout_row_mod < 0 || (p->dout_row_mod > 0 && f.dim % p->dout_row_mod != 0)) return OSS_ERR_SHAPE;
-    const int v = bwd_variant_for(f.batch, f.dim, f.seqlen, f.dstate, f.n_groups, p->tune_variant);
+    rc = check_bwd_shape(p);
+    if (rc != OSS_OK) return rc;
+    int v;
+    ScanBwdPlan pl;
+    rc = plan_bwd(*p, io, v, pl);
     g_last_bwd.store(v);
+    g_last_bwd_segments.store(rc == OSS_OK ? pl.seg.n_seg : 1);
+    g_last_bwd_lane_states.store(rc == OSS_OK && pl.lane_states ? 1 : 0);
+    if (rc != OSS_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ProfTimer prof(1, v, (int)io, bwd_alg_bytes(f, eb), bwd_own_bytes(*p, eb));
     ProfTimer fprof(2, v, (int)io, 0.0);   // the finishing kernel of the same call
-    const int sr = p->tune_segments > 0 ? p->tune_segments : g_force_bwd_seg.load();
-    g_last_bwd_lane_states.store(0);
-    return io_dispatch(io, [&](auto tag) { return scan_bwd_dispatch<typename decltype(tag)::type>(*p, v, sr, s, &prof, &fprof); });
+    if (pl.seg.n_seg > 1) { prof.segmented(); fprof.segmented(); }
+    return io_dispatch(io, [&](auto tag) { return scan_bwd_dispatch<typename decltype(tag)::type>(*p, pl, s, &prof, &fprof); });
 }
 
 int oss_dwconv3x3_fwd(oss_dtype io, const void *x, const float *weight, const float *bias, void *y, void *pre_silu, int batch,

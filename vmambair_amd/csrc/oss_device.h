@@ -7,15 +7,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "oss_scan_plan.h"   // kScanChunk, kNB, kMaxDtRank, lane_state_stride, the tile padding: shared with the host plan
 
 namespace oss {
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
-constexpr int kScanChunk = 256;  // time steps between saved states in x (oss_scan_chunk())
-constexpr int kNB = 16;          // states per LDS tile
-// lane states (include/vmambair_oss.h: hs): entries per (batch, row, state) line, one per 8 scan steps, padded to whole 512-step chunks
-__host__ __device__ inline size_t lane_state_stride(int seqlen) { return (size_t)(((seqlen + 7) / 8 + 63) & ~63); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -210,8 +207,8 @@ __device__ __forceinline__ int tile_off(int n, int p, int i) {
 // profiles/r04_pmc_sq_scan.txt: SQ_LDS_BANK_CONFLICT = 25 % of SQ_LDS_IDX_ACTIVE for oss_scan_fwd_kernel<bf16,64,16,12>.
 // With 128 / I floats of padding per plane a group's 8 threads -- 8 / (I/4) positions x I/4 quads -- cover the 8 slots of the
 // sweep once (16 floats were measured first: 25 % -> 10 %, quads 0 / 2 still on one slot).
-template <int I> constexpr int kTilePlanePad = 128 / I;
-template <int LPR, int I> constexpr int kTileRowPad = LPR * I + (I / 4) * kTilePlanePad<I>;   // floats per state row
+template <int I> constexpr int kTilePlanePad = tile_plane_pad(I);
+template <int LPR, int I> constexpr int kTileRowPad = tile_row_pad(LPR, I);   // floats per state row
 template <int LPR, int I>
 __device__ __forceinline__ int tile_off_pad(int n, int p, int i) {
     return n * kTileRowPad<LPR, I> + (i >> 2) * (LPR * 4 + kTilePlanePad<I>) + p * 4 + (i & 3);
@@ -322,7 +319,6 @@ __device__ __forceinline__ void unpack_raw_dir(const RawItems<T, I> &r, bool rev
 // Split in two so that a kernel can put the loads of ALL rank rows in flight together with its other chunk loads (u, dout):
 // every dependent global load is a full memory round trip (~1 us measured for rows another XCD has just written), and a loop
 // that loads, converts and accumulates row by row pays it once per row (+70 us on the u:(8,384,4096) backward).
-constexpr int kMaxDtRank = 8;
 template <typename T, int I> struct DtRows {
     RawItems<T, I> z[kMaxDtRank];
     float w[kMaxDtRank];

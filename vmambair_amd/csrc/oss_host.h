@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/vmambair_oss.h"
+#include "oss_scan_plan.h"
 
 #include <atomic>
 #include <initializer_list>
@@ -30,7 +31,6 @@ inline int io_bytes(oss_dtype io) { return io == OSS_F32 ? 4 : io_ok<IO_16>(io) 
 // Dynamic LDS above the 48 KiB default has to be enabled per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).
 // One gate per kernel instantiation: what has been enabled so far, one lock-free slot per device, so that a process driving
 // several GPUs (or several host threads) never launches with a stale assumption.
-constexpr size_t kMaxLdsBytes = 160 * 1024;   // gfx950: 160 KiB per workgroup
 struct LdsGate {
     std::atomic<size_t> enabled[16] = {};
     int ensure(const void *kern, size_t bytes) {
@@ -54,35 +54,19 @@ struct LdsGate {
 // forward pass for the backward (`HS`, DESIGN.md section 9: chosen per call by oss_scan_fwd_params.hs).  oss_scan_features()
 // reports both bits.
 
-// Time-segmented launches (oss_scan_fwd.hip: FwdSeg, oss_scan_bwd_v2.h: BwdSeg).  seg_req: -1 = heuristic, 0 / 1 = never,
-// n > 1 = n segments (clamped to the number of chunks).
-constexpr int kMaxSegments = 64;
-int scan_pick_segments(long wgs, int n_chunks, int seg_req, double ovh);
-inline size_t scan_carry_bytes(int batch, int dim, int dstate, int n_seg) {
-    return sizeof(float) * 2 * (size_t)batch * dim * dstate * n_seg;
-}
-extern std::atomic<int> g_last_fwd_segments, g_last_bwd_segments, g_last_bwd_lane_states;
-// pieces of the first (local / carry) launch per main segment: the largest piece count c <= forced (forced > 0), or with
-// wgs * (n_seg - 1) * c <= 512 (heuristic), whose n_seg * c carry slots fit what the workspace queries allow.  A main segment
-// of cps chunks is cut into c pieces of ceil(cps / c) chunks, the last one shorter (oss_scan_set_carry_split)
-int scan_carry_split(long wgs, int n_seg, int cps, int n_chunks, int per_call = 0);
+// The scan launchers run a plan (oss_scan_plan.h: what to launch is decided there, once per call) and nothing else.
 // the dt-factor gradient inside the backward's finishing launch (oss_scan_bwd_params.finish_dt_weight): whole 8 / 16-byte quads
 inline bool scan_finish_dt_ok(int seqlen, int rank) { return seqlen > 0 && seqlen % 4 == 0 && rank >= 1 && rank <= 8; }
-template <typename T> int scan_fwd_dispatch(const oss_scan_fwd_params &p, int variant, int seg_req, hipStream_t stream);
-// one timer brackets the MAIN backward kernel, a second one the finishing kernel (oss_prof_* buckets 1 and 2)
+template <typename T> int scan_fwd_dispatch(const oss_scan_fwd_params &p, const ScanFwdPlan &plan, hipStream_t stream);
+// one timer brackets the MAIN backward launches (carry pass included), a second one the finishing kernel (oss_prof_* buckets 1 and 2)
 struct LaunchTimer {
     virtual void begin(hipStream_t) = 0;
     virtual void end(hipStream_t) = 0;
-    virtual void segmented() {}   // the launch about to be timed is a time-segmented one (its own profiler bucket)
     virtual ~LaunchTimer() = default;
 };
 template <typename T>
-int scan_bwd_dispatch(const oss_scan_bwd_params &p, int variant, int seg_req, hipStream_t stream, LaunchTimer *timer,
-                      LaunchTimer *finish_timer = nullptr);
+int scan_bwd_dispatch(const oss_scan_bwd_params &p, const ScanBwdPlan &plan, hipStream_t stream, LaunchTimer *timer, LaunchTimer *finish_timer);
 
-// number of row tiles the backward splits a group into for `variant` (workspace sizing)
-int scan_bwd_rows_per_wg(int variant);
-int scan_bwd_pick_variant(int batch, int dim, int seqlen, int dstate, int n_groups);
 int dwconv3x3(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int C, int H, int W,
               int64_t xsb, int64_t xsc, int64_t ysb, int64_t ysc, int flip, hipStream_t s, void *pre = nullptr, int act = 0);
 // the convolution fused with what follows it (oss_dwconv.hip): mode 0 = silu (SS2D_1), 1 = gelu gate of the EFFN
@@ -241,5 +225,4 @@ int pixel_loss_fwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, 
 int pixel_loss_bwd(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, const void *pred, const void *target, const float *weight,
                    const double *stats, const float *grad_output, void *dpred, int64_t N, int64_t C, int64_t plane, float loss_weight,
                    float eps, hipStream_t s);
-int scan_fwd_pick_variant(int batch, int dim, int seqlen, int dstate, int n_groups, int elem_bytes);
 }  // namespace oss

@@ -35,9 +35,6 @@ struct BwdWs {
     float *bc, *dA, *dD, *db, *dW;
     int tiles, rp;
 };
-__host__ __device__ inline size_t ws_bc_floats(int batch, int G, int tiles, int N, int L, int RP = 0) {
-    return (size_t)batch * G * tiles * (2 * N + RP) * L;
-}
 
 // SPS: states walked together between two barriers (2: two independent dependency chains per wave for the
 // scheduler to interleave and half the barriers, at twice the slab LDS and ~2x the registers -- for grids
@@ -532,41 +529,20 @@ oss_scan_bwd_finish(const FinishArgs a) {
 #include "oss_scan_bwd_v2.h"
 namespace oss {
 
-static thread_local LaunchTimer *g_finish_timer = nullptr;   // set by scan_bwd_dispatch around the launchers
-
-// workspace carving shared by the launchers; -> OSS_OK or OSS_ERR_WORKSPACE.  n_seg > 1 (time-segmented launch): one
-// weight-gradient partial per (batch, segment, row) and, behind them, the reverse-carry pairs (*carry).
-static int carve_ws(const oss_scan_bwd_params &p, int rows_per_wg, BwdWs &ws, float *&wdD, float *&wdb, int n_seg = 1,
-                    float **carry = nullptr, int n_cseg = 0) {
-    const oss_scan_fwd_params &f = p.f;
-    const int rows_per_group = f.dim / f.n_groups;
-    const int tiles = (rows_per_group + rows_per_wg - 1) / rows_per_wg;
-    const int rp = f.dt_weight ? f.dt_rank : 0;
-    const size_t n_bc = ws_bc_floats(f.batch, f.n_groups, tiles, f.dstate, f.seqlen, rp);
-    const size_t wb = (size_t)f.batch * n_seg;
-    const size_t n_w = wb * f.dim * (f.dstate + 2 + (rp ? kMaxDtRank : 0));
-    const size_t n_carry = n_seg > 1 ? scan_carry_bytes(f.batch, f.dim, f.dstate, std::max(n_seg, n_cseg)) / sizeof(float) : 0;
-    const size_t need = sizeof(float) * (n_bc + n_w + n_carry);
-    if (!p.workspace || p.workspace_bytes < need) return OSS_ERR_WORKSPACE;
-    ws.bc = reinterpret_cast<float *>(p.workspace);
-    ws.dA = ws.bc + n_bc;
-    ws.dD = ws.dA + wb * f.dim * f.dstate;
-    ws.db = ws.dD + wb * f.dim;
-    ws.dW = rp ? ws.db + wb * f.dim : nullptr;
-    if (carry) *carry = ws.bc + n_bc + n_w;
-    ws.tiles = tiles;
-    ws.rp = rp;
-    wdD = ws.dD; wdb = ws.db;
-    if (!p.dD) ws.dD = nullptr;
-    if (!p.ddelta_bias) ws.db = nullptr;
-    return OSS_OK;
+// the plan's carving of the caller's workspace (oss_scan_plan.h: ScanBwdWs) as the kernels' pointers
+static BwdWs plan_ws(const oss_scan_bwd_params &p, const ScanBwdWs &w) {
+    float *base = reinterpret_cast<float *>(p.workspace);
+    return BwdWs{base + w.bc, base + w.dA, p.dD ? base + w.dD : nullptr, p.ddelta_bias ? base + w.db : nullptr,
+                 w.rp ? base + w.dW : nullptr, w.tiles, w.rp};
 }
 
-template <typename T, bool PB = false>
-static int launch_finish(const oss_scan_bwd_params &p, const BwdWs &ws, float *wdD, float *wdb, hipStream_t stream, int n_seg = 1) {
+template <typename T, bool PB>
+static int launch_finish(const oss_scan_bwd_params &p, const ScanBwdPlan &pl, hipStream_t stream, LaunchTimer *timer) {
     const oss_scan_fwd_params &f = p.f;
+    const BwdWs ws = plan_ws(p, pl.ws);
+    float *wdD = reinterpret_cast<float *>(p.workspace) + pl.ws.dD, *wdb = reinterpret_cast<float *>(p.workspace) + pl.ws.db;
     FinishArgs a;
-    a.wbatch = f.batch * n_seg;
+    a.wbatch = pl.ws.wbatch;
     a.ws_bc = ws.bc; a.dB = p.dB; a.dC = p.dC; a.dZ = p.ddt;
     a.tiles = ws.tiles; a.N = f.dstate; a.RP = ws.rp; a.R = ws.rp ? f.dt_rank : 0; a.G = f.n_groups;
     a.L = (size_t)f.seqlen;
@@ -603,176 +579,77 @@ static int launch_finish(const oss_scan_bwd_params &p, const BwdWs &ws, float *w
     const unsigned dt_slabs = a.dt_blocks ? (a.dt_blocks + gx * gy - 1) / (gx * gy) : 0;
     if ((size_t)f.batch * f.n_groups + 1 + dt_slabs > 65535) return OSS_ERR_SHAPE;
     const dim3 grid(gx, gy, (unsigned)(f.batch * f.n_groups + 1) + dt_slabs);
-    if (g_finish_timer) g_finish_timer->begin(stream);
+    if (timer) timer->begin(stream);
     if (vec) hipLaunchKernelGGL((oss_scan_bwd_finish<T, 4, PB>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((oss_scan_bwd_finish<T, 1, PB>), grid, dim3(256), 0, stream, a);
-    if (g_finish_timer) g_finish_timer->end(stream);
-    return (int)hipGetLastError();
-}
-
-template <typename K, typename... Extra>
-static int launch_main(K kern, size_t smem, LdsGate &gate, unsigned nblocks, int nthreads,
-                       const oss_scan_bwd_params &p, const BwdWs &ws, hipStream_t stream, LaunchTimer *timer, Extra... extra) {
-    if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;
-    if (timer) timer->begin(stream);
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(nthreads), smem, stream, p, ws, extra...);
     if (timer) timer->end(stream);
     return (int)hipGetLastError();
 }
 
-template <typename T, int LPR, int I, int WAVES, int NBB, int SPS, int MINW>
-static int launch_bwd(const oss_scan_bwd_params &p, hipStream_t stream, LaunchTimer *timer) {
-    constexpr int ROWS = WAVES * (64 / LPR);
-    constexpr int TC = LPR * I;
-    const oss_scan_fwd_params &f = p.f;
-    BwdWs ws;
-    float *wdD, *wdb;
-    int rc = carve_ws(p, ROWS, ws, wdD, wdb);
-    if (rc != OSS_OK) return rc;
-    const size_t smem = sizeof(float) * (2 * (size_t)NBB * TC + 2 * (size_t)SPS * ROWS * TC + 3 * (size_t)f.dstate * ROWS + ROWS);
-    if constexpr (!(I == 4 && WAVES == 4)) {
-        // large dstate: the per-row state tables no longer fit next to the tiles and slabs -> the small-shape variant.  The
-        // workspace was carved for THIS variant's row tiles, so it is carved again there (the query sizes for 4-row tiles)
-        if (smem > kMaxLdsBytes) return launch_bwd<T, 64, 4, 4, 16, 1, 3>(p, stream, timer);
-    }
+// one launch of one main-kernel instantiation, with that instantiation's own LDS gate
+template <auto Kern, typename... Extra>
+static int launch_main(const ScanBwdPlan &pl, int nthreads, const oss_scan_bwd_params &p, const BwdWs &ws, hipStream_t stream, Extra... extra) {
     static LdsGate gate;
-    rc = launch_main(oss_scan_bwd_kernel<T, LPR, I, WAVES, NBB, SPS, MINW>, smem, gate,
-                     (unsigned)(f.batch * f.n_groups * ws.tiles), WAVES * 64, p, ws, stream, timer);
-    if (rc != OSS_OK) return rc;
-    return launch_finish<T>(p, ws, wdD, wdb, stream);
+    if (const int e = gate.ensure(reinterpret_cast<const void *>(Kern), pl.lds_bytes)) return e;
+    hipLaunchKernelGGL(Kern, dim3((unsigned)(pl.wgs * pl.seg.n_seg)), dim3(nthreads), pl.lds_bytes, stream, p, ws, extra...);
+    return (int)hipGetLastError();
 }
 
-// round-2 kernel (oss_scan_bwd_v2.h): lane-resident per-state scalars, register-prefetched tiles, one barrier per state
-template <typename T, int WAVES, int NBB, int MINW, bool FD = false, bool PB = false>
-static int launch_bwd2(const oss_scan_bwd_params &p, int seg_req, hipStream_t stream, LaunchTimer *timer) {
-    if constexpr (!FD) {
-        if (p.f.dt_weight) return launch_bwd2<T, WAVES, NBB, MINW, true>(p, seg_req, stream, timer);
-    }
-    constexpr int TC = 512;
-    const oss_scan_fwd_params &f = p.f;
-    const int rows_per_group = f.dim / f.n_groups;
-    const int tiles = (rows_per_group + WAVES - 1) / WAVES;
-    if constexpr (!PB && kPartialsBf16Ok<T, FD>) {
-        // bf16 row-tile partials (oss_scan_bwd_v2.h: kPartialsBf16Ok): only when THIS call asks for them (tune_partials == 2)
-        const bool lane_states = f.hs != nullptr;
-        if (p.tune_partials == 2 && !lane_states)
-            return launch_bwd2<T, WAVES, NBB, MINW, false, true>(p, seg_req, stream, timer);
-    }
-    const unsigned wgs = (unsigned)(f.batch * f.n_groups * tiles);
-    const int n_chunks = (f.seqlen + TC - 1) / TC;
-    int n_seg = FD ? 1 : scan_pick_segments(wgs, n_chunks, seg_req, 0.3);
-    int cps = n_chunks;
-    if (n_seg > 1) { cps = (n_chunks + n_seg - 1) / n_seg; n_seg = (n_chunks + cps - 1) / cps; }
-    // carry segments per main segment (BwdSeg; oss_host.h: scan_carry_split)
-    int csub = scan_carry_split((long)wgs, n_seg, cps, n_chunks, f.tune_carry_split);
-    int ccps = (cps + csub - 1) / csub, n_cseg = n_seg > 1 ? n_seg * csub : 0;
-    BwdWs ws;
-    float *wdD, *wdb, *carry = nullptr;
-    int rc = carve_ws(p, WAVES, ws, wdD, wdb, n_seg, &carry, n_cseg);
-    if (rc != OSS_OK && n_seg > 1 && csub > 1) {   // room for the main segments' carry pairs but not the finer pieces' 
-        csub = 1; ccps = cps; n_cseg = n_seg;
-        rc = carve_ws(p, WAVES, ws, wdD, wdb, n_seg, &carry, n_cseg);
-    }
-    if (rc != OSS_OK && n_seg > 1) {   // a caller that sized the workspace for the unsegmented form
-        n_seg = 1; cps = n_chunks;
-        rc = carve_ws(p, WAVES, ws, wdD, wdb);
-    }
-    if (rc != OSS_OK) return rc;
-    g_last_bwd_segments.store(n_seg);
-    // lane states saved by the forward pass (f.hs): the kernels that load them instead of re-running the forward recurrence
-    const bool hs = !FD && !PB && f.hs != nullptr;
-    // two tile buffers, two slab buffers (+ dt weights | + two buffers of this wave's lane states)
-    const bool slab_q = !FD && !(hs && WAVES > 8);   // oss_scan_bwd2_kernel: SQ
-    const size_t smem = sizeof(float) * (4 * (size_t)NBB * TC + 4 * (size_t)WAVES * (slab_q ? kSlabA : TC) +
-                                         (FD ? WAVES * kMaxDtRank : 0) + (hs ? 2 * (size_t)WAVES * NBB * 64 : 0));
-    g_last_bwd_lane_states.store(hs ? 1 : 0);
-    if constexpr (!FD) {
-        if (n_seg > 1) {
-            const BwdSeg sg{carry, n_seg, cps, csub, ccps, n_cseg};
-            // the carry pass is per ROW (nothing is summed over rows), so its row tile is free; it uses the main kernel's: 4-row
-            // workgroups (three times the workgroups, several per CU) measured SLOWER -- u:(4,192,16384) 0.355 against 0.340 ms for
-            // the whole call -- because every workgroup stages the group's C rows again
-            constexpr int CW = WAVES;
-            const int ctiles = (rows_per_group + CW - 1) / CW;
-            auto kc = oss_scan_bwd_carry_kernel<T, CW>;
-            if (timer) { timer->segmented(); timer->begin(stream); }
-            if (g_finish_timer) g_finish_timer->segmented();
-            hipLaunchKernelGGL(kc, dim3((unsigned)(f.batch * f.n_groups * ctiles * (n_cseg - csub))), dim3(CW * 64), sizeof(float) * 2 * kNB * TC,
-                               stream, p, sg, ctiles);
-            static LdsGate gate_s, gate_sh;
-            bool launched = false;
-            if constexpr (!PB) {
-                if (hs) {
-                    auto km = oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, true, true>;
-                    if (const int e = gate_sh.ensure(reinterpret_cast<const void *>(km), smem)) return e;
-                    hipLaunchKernelGGL(km, dim3(wgs * (unsigned)n_seg), dim3(WAVES * 64), smem, stream, p, ws, sg);
-                    launched = true;
-                }
-            }
-            if (!launched) {
-                auto km = oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, true, false, PB>;
-                if (const int e = gate_s.ensure(reinterpret_cast<const void *>(km), smem)) return e;
-                hipLaunchKernelGGL(km, dim3(wgs * (unsigned)n_seg), dim3(WAVES * 64), smem, stream, p, ws, sg);
-            }
-            if (timer) timer->end(stream);
-            rc = (int)hipGetLastError();
-            if (rc != OSS_OK) return rc;
-            return launch_finish<T, PB>(p, ws, wdD, wdb, stream, n_seg);
-        }
-        if constexpr (!PB) {
-            if (hs) {
-                static LdsGate gate_h;
-                rc = launch_main(oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, false, true>, smem, gate_h, wgs, WAVES * 64, p, ws,
-                                 stream, timer, BwdSeg{nullptr, 1, n_chunks, 1, n_chunks, 1});
-                if (rc != OSS_OK) return rc;
-                return launch_finish<T, false>(p, ws, wdD, wdb, stream);
-            }
-        }
-    }
-    static LdsGate gate;
-    rc = launch_main(oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, FD, false, false, PB>, smem, gate, wgs, WAVES * 64, p, ws, stream, timer,
-                     BwdSeg{nullptr, 1, n_chunks, 1, n_chunks, 1});
-    if (rc != OSS_OK) return rc;
-    return launch_finish<T, PB>(p, ws, wdD, wdb, stream);
-}
-
-// variant table (numbers kept from rounds 1-3; 0 and 2..9 -- the other round-1 row tiles and the packed two-states-per-pass
-// kernels, all measured slower than the round-2 kernel -- were removed in round 4 and now mean variant 1):
-//   1: round-1 kernel, 64 lanes x 4 items, 4 rows/WG, 16 states per LDS tile (TC 256, 40 KiB LDS): short sequences, few rows
-//      per group, dstate > 64 (the round-2 kernel keeps one lane per state) and the fallback when a launch would not fit LDS
-//  10: round-2 kernel (oss_scan_bwd_v2.h), 12 rows/WG (128 KiB LDS)   11: 8 rows/WG   12: 6 rows/WG   13: 4 rows/WG
-static const int kBwdRows[] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 12, 8, 6, 4};
-int scan_bwd_rows_per_wg(int variant) { return kBwdRows[(variant < 0 || variant > 13) ? 1 : variant]; }
-
+// round-1 kernel: never cut in time, fp32 partials
 template <typename T>
-static int scan_bwd_dispatch_(const oss_scan_bwd_params &p, int variant, int seg_req, hipStream_t stream, LaunchTimer *timer);
-template <typename T>
-int scan_bwd_dispatch(const oss_scan_bwd_params &p, int variant, int seg_req, hipStream_t stream, LaunchTimer *timer,
-                      LaunchTimer *finish_timer) {
-    g_finish_timer = finish_timer;
-    g_last_bwd_segments.store(1);
-    const int rc = scan_bwd_dispatch_<T>(p, variant, seg_req, stream, timer);
-    g_finish_timer = nullptr;
-    return rc;
-}
-template <typename T>
-static int scan_bwd_dispatch_(const oss_scan_bwd_params &p, int variant, int seg_req, hipStream_t stream, LaunchTimer *timer) {
-    if (p.f.dt_weight) {   // delta computed inside the scan: round-2 kernels only
-        if (p.f.dstate > 64 || p.f.dt_rank < 1 || p.f.dt_rank > kMaxDtRank || !p.ddt || !p.ddt_weight) return OSS_ERR_SHAPE;
-        if (variant < 10) variant = 13;
-    }
-    if (variant >= 10 && p.f.dstate > 64) variant = 1;   // the round-2 kernel keeps one lane per state
-    switch (variant) {
-        case 10: return launch_bwd2<T, 12, 4, 3>(p, seg_req, stream, timer);
-        case 11: return launch_bwd2<T, 8, 4, 2>(p, seg_req, stream, timer);
-        case 12: return launch_bwd2<T, 6, 4, 2>(p, seg_req, stream, timer);
-        case 13: return launch_bwd2<T, 4, 4, 2>(p, seg_req, stream, timer);   // 4-row workgroups for calls with few rows (one wave per SIMD, no spills)
-        default: return launch_bwd<T, 64, 4, 4, 16, 1, 3>(p, stream, timer);
-    }
+static int launch_bwd1(const oss_scan_bwd_params &p, const ScanBwdPlan &pl, hipStream_t stream) {
+    return launch_main<oss_scan_bwd_kernel<T, 64, 4, 4, kBwd1TileStates, 1, 3>>(pl, 4 * 64, p, plan_ws(p, pl.ws), stream);
 }
 
-template int scan_bwd_dispatch<float>(const oss_scan_bwd_params &, int, int, hipStream_t, LaunchTimer *, LaunchTimer *);
-template int scan_bwd_dispatch<bf16_t>(const oss_scan_bwd_params &, int, int, hipStream_t, LaunchTimer *, LaunchTimer *);
-template int scan_bwd_dispatch<f16_t>(const oss_scan_bwd_params &, int, int, hipStream_t, LaunchTimer *, LaunchTimer *);
+// round-2 kernel (oss_scan_bwd_v2.h): lane-resident per-state scalars, register-prefetched tiles, one barrier per state.
+// The forms of the plan: FD (fused delta; never segmented), else SEG (time segments) x { HS (lane states) | PB (bf16 partials) | plain }
+template <typename T, int WAVES, int MINW, bool SEG>
+static int launch_bwd2_form(const oss_scan_bwd_params &p, const ScanBwdPlan &pl, const BwdWs &ws, const BwdSeg &sg, hipStream_t stream) {
+    constexpr int NBB = kBwd2TileStates;
+    if (pl.lane_states) return launch_main<oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, SEG, true, false>>(pl, WAVES * 64, p, ws, stream, sg);
+    if constexpr (kPartialsBf16Ok<T, false>) {
+        if (pl.bf16_partials) return launch_main<oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, SEG, false, true>>(pl, WAVES * 64, p, ws, stream, sg);
+    }
+    return launch_main<oss_scan_bwd2_kernel<T, WAVES, NBB, MINW, false, SEG, false, false>>(pl, WAVES * 64, p, ws, stream, sg);
+}
+template <typename T, int WAVES, int MINW>
+static int launch_bwd2(const oss_scan_bwd_params &p, const ScanBwdPlan &pl, hipStream_t stream) {
+    const ScanSegs &s = pl.seg;
+    const BwdWs ws = plan_ws(p, pl.ws);
+    const BwdSeg sg{s.n_seg > 1 ? reinterpret_cast<float *>(p.workspace) + pl.ws.carry : nullptr, s.n_seg, s.cps, s.csub, s.ccps, s.n_cseg};
+    if (pl.fused_delta) return launch_main<oss_scan_bwd2_kernel<T, WAVES, kBwd2TileStates, MINW, true>>(pl, WAVES * 64, p, ws, stream, sg);
+    if (s.n_seg == 1) return launch_bwd2_form<T, WAVES, MINW, false>(p, pl, ws, sg, stream);
+    // the carry pass is per ROW (nothing is summed over rows), so its row tile is free; it uses the main kernel's: 4-row
+    // workgroups (three times the workgroups, several per CU) measured SLOWER -- u:(4,192,16384) 0.355 against 0.340 ms for
+    // the whole call -- because every workgroup stages the group's C rows again
+    hipLaunchKernelGGL((oss_scan_bwd_carry_kernel<T, WAVES>), dim3((unsigned)(pl.wgs * (s.n_cseg - s.csub))), dim3(WAVES * 64),
+                       sizeof(float) * 2 * kNB * pl.kernel.chunk, stream, p, sg, pl.tiles);
+    return launch_bwd2_form<T, WAVES, MINW, true>(p, pl, ws, sg, stream);
+}
+
+// runs the plan (oss_scan_plan.h): the main launches of the plan's kernel shape (table: kScanBwdShapes) under `timer`, then the
+// finishing launch under `finish_timer`
+template <typename T>
+int scan_bwd_dispatch(const oss_scan_bwd_params &p, const ScanBwdPlan &pl, hipStream_t stream, LaunchTimer *timer, LaunchTimer *finish_timer) {
+    int rc;
+    if (timer) timer->begin(stream);
+    switch (pl.kernel.variant) {
+        case 10: rc = launch_bwd2<T, 12, 3>(p, pl, stream); break;
+        case 11: rc = launch_bwd2<T, 8, 2>(p, pl, stream); break;
+        case 12: rc = launch_bwd2<T, 6, 2>(p, pl, stream); break;
+        case 13: rc = launch_bwd2<T, 4, 2>(p, pl, stream); break;   // 4-row workgroups for calls with few rows (one wave per SIMD, no spills)
+        default: rc = launch_bwd1<T>(p, pl, stream); break;
+    }
+    if (timer) timer->end(stream);
+    if (rc != OSS_OK) return rc;
+    if constexpr (kPartialsBf16Ok<T, false>) {
+        if (pl.bf16_partials) return launch_finish<T, true>(p, pl, stream, finish_timer);
+    }
+    return launch_finish<T, false>(p, pl, stream, finish_timer);
+}
+
+template int scan_bwd_dispatch<float>(const oss_scan_bwd_params &, const ScanBwdPlan &, hipStream_t, LaunchTimer *, LaunchTimer *);
+template int scan_bwd_dispatch<bf16_t>(const oss_scan_bwd_params &, const ScanBwdPlan &, hipStream_t, LaunchTimer *, LaunchTimer *);
+template int scan_bwd_dispatch<f16_t>(const oss_scan_bwd_params &, const ScanBwdPlan &, hipStream_t, LaunchTimer *, LaunchTimer *);
 
 }  // namespace oss

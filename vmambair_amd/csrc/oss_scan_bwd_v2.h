@@ -109,8 +109,7 @@ template <typename T, bool FD> constexpr bool kPartialsBf16Ok = !FD && std::is_s
 // 16-byte pieces; kSlabK = 256 + 32 puts the second quads half a bank sweep away from the first ones, so that the summing
 // lanes -- lane s reads quad (s & 1) of position base + (s >> 1), i.e. scan positions base * 8 + 4 s: the partial rows still
 // leave as fully coalesced 16-byte stores -- are conflict-free too.
-constexpr int kSlabK = 288;            // floats between the two quads of a lane
-constexpr int kSlabA = 2 * kSlabK;     // floats per (row, dB | dC) array
+// (kSlabK = 288 floats between the two quads of a lane, kSlabA = 2 kSlabK floats per (row, dB | dC) array: oss_scan_plan.h)
 // SEG: time-segmented launch (workgroup = (batch, group, row tile, SEGMENT of cps chunks)) for calls whose row-tile grid
 // leaves CUs idle.  The reference walks a row's chunks last to first inside one block (cus/selective_scan_bwd_kernel.cuh:
 // 120-125,184); here a segment starts from (a) the forward state saved in x -- free, x holds one every 256 steps -- and

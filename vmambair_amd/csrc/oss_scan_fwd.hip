@@ -274,81 +274,43 @@ oss_scan_fwd_kernel(const oss_scan_fwd_params p, const FwdSeg sg) {
     }
 }
 
-template <typename T, int LPR, int I, int WAVES, bool FD = false>
-static int launch_fwd(const oss_scan_fwd_params &p, int seg_req, hipStream_t stream) {
-    if constexpr (!FD) {
-        if (p.dt_weight) return launch_fwd<T, LPR, I, WAVES, true>(p, seg_req, stream);
-    }
-    constexpr int ROWS = WAVES * (64 / LPR);
-    constexpr int TC = LPR * I;
-    const int rows_per_group = p.dim / p.n_groups;
-    const int tiles = (rows_per_group + ROWS - 1) / ROWS;
-    constexpr int TR = kTileRowPad<LPR, I>;
-    const size_t smem = sizeof(float) * (2 * (size_t)kNB * TR + 3 * (size_t)p.dstate * ROWS);
-    if constexpr (!(LPR == 64 && I == 4 && WAVES == 4)) {
-        // large dstate: tiles + per-row carries no longer fit 160 KiB -> the small-shape variant (4 rows, 256-step chunks)
-        if (smem > kMaxLdsBytes) return launch_fwd<T, 64, 4, 4, FD>(p, seg_req, stream);
-    }
-    const unsigned wgs = (unsigned)(p.batch * p.n_groups * tiles);
-    const int n_chunks = (p.seqlen + TC - 1) / TC;
-    int n_seg = FD ? 1 : scan_pick_segments(wgs, n_chunks, seg_req, 0.55);
-    // the carry slots are per LOCAL-pass piece.  A caller's workspace that holds the main segments' slots but not the finer
-    // pieces' keeps the segments and drops the finer split; only one that does not hold even those goes unsegmented
-    if (n_seg > 1 && !p.workspace) n_seg = 1;
-    g_last_fwd_segments.store(1);
-    if constexpr (!FD) {
-        if (n_seg > 1) {
-            FwdSeg sg;
-            sg.carry = reinterpret_cast<float *>(p.workspace);
-            sg.cps = (n_chunks + n_seg - 1) / n_seg;
-            sg.n_seg = (n_chunks + sg.cps - 1) / sg.cps;
-            sg.csub = scan_carry_split((long)wgs, sg.n_seg, sg.cps, n_chunks, p.tune_carry_split);
-            if (p.workspace_bytes < scan_carry_bytes(p.batch, p.dim, p.dstate, sg.n_seg * sg.csub)) sg.csub = 1;
-            sg.ccps = (sg.cps + sg.csub - 1) / sg.csub;
-            sg.n_cseg = sg.n_seg * sg.csub;
-            if (p.workspace_bytes < scan_carry_bytes(p.batch, p.dim, p.dstate, sg.n_cseg)) sg.n_seg = 1;
-          if (sg.n_seg > 1) {
-            g_last_fwd_segments.store(sg.n_seg);
-            auto k1 = oss_scan_fwd_kernel<T, LPR, I, WAVES, false, 1>;
-            auto k2 = oss_scan_fwd_kernel<T, LPR, I, WAVES, false, 2>;
-            static LdsGate gate1, gate2;
-            if (const int e = gate1.ensure(reinterpret_cast<const void *>(k1), smem)) return e;
-            if (const int e = gate2.ensure(reinterpret_cast<const void *>(k2), smem)) return e;
-            hipLaunchKernelGGL(k1, dim3(wgs * (unsigned)((sg.n_seg - 1) * sg.csub)), dim3(WAVES * 64), smem, stream, p, sg);
-            hipLaunchKernelGGL(k2, dim3(wgs * (unsigned)sg.n_seg), dim3(WAVES * 64), smem, stream, p, sg);
-            return (int)hipGetLastError();
-          }
-        }
-    }
-    auto kern = oss_scan_fwd_kernel<T, LPR, I, WAVES, FD, 0>;
+// one launch of one kernel instantiation, with that instantiation's own LDS gate
+template <auto Kern>
+static int launch_fwd_kernel(long blocks, int threads, size_t smem, hipStream_t stream, const oss_scan_fwd_params &p, const FwdSeg &sg) {
     static LdsGate gate;
-    if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3(WAVES * 64), smem, stream, p, FwdSeg{nullptr, 1, n_chunks, 1, n_chunks, 1});
+    if (const int e = gate.ensure(reinterpret_cast<const void *>(Kern), smem)) return e;
+    hipLaunchKernelGGL(Kern, dim3((unsigned)blocks), dim3(threads), smem, stream, p, sg);
     return (int)hipGetLastError();
 }
 
-// variant table: (lanes per row, items per lane, waves per workgroup)
-//   0: 64 x 8  x 8   (TC  512,  8 rows/WG)   many waves for small batches
-//   1: 32 x 16 x 8   (TC  512, 16 rows/WG)
-//   2: 16 x 16 x 4   (TC  256, 16 rows/WG)   fewest scan steps, needs many rows
-//   3: 64 x 16 x 8   (TC 1024,  8 rows/WG)
-//   4: 64 x 4  x 4   (TC  256,  4 rows/WG)   short sequences / few rows per group
-//   6: 64 x 16 x 12  (TC 1024, 12 rows/WG): row counts that give <= 256 such workgroups
-//   (5 = 64 x 8 x 12 and 7 = 64 x 16 x 6 were never picked by scan_fwd_pick_variant: removed in round 4, the numbers now mean 4)
+// runs the plan (oss_scan_plan.h): the local pass + the real pass of a time-segmented call, else the one unsegmented launch
+template <typename T, int LPR, int I, int WAVES>
+static int launch_fwd(const oss_scan_fwd_params &p, const ScanFwdPlan &pl, hipStream_t stream) {
+    const ScanSegs &s = pl.seg;
+    const FwdSeg sg{s.n_seg > 1 ? reinterpret_cast<float *>(p.workspace) : nullptr, s.n_seg, s.cps, s.csub, s.ccps, s.n_cseg};
+    constexpr int NT = WAVES * 64;
+    if (pl.fused_delta) return launch_fwd_kernel<oss_scan_fwd_kernel<T, LPR, I, WAVES, true, 0>>(pl.wgs, NT, pl.lds_bytes, stream, p, sg);
+    if (s.n_seg == 1) return launch_fwd_kernel<oss_scan_fwd_kernel<T, LPR, I, WAVES, false, 0>>(pl.wgs, NT, pl.lds_bytes, stream, p, sg);
+    if (const int e = launch_fwd_kernel<oss_scan_fwd_kernel<T, LPR, I, WAVES, false, 1>>(pl.wgs * (s.n_seg - 1) * s.csub, NT, pl.lds_bytes, stream, p, sg))
+        return e;
+    return launch_fwd_kernel<oss_scan_fwd_kernel<T, LPR, I, WAVES, false, 2>>(pl.wgs * s.n_seg, NT, pl.lds_bytes, stream, p, sg);
+}
+
+// the instantiation of the plan's kernel shape (table: oss_scan_plan.h, kScanFwdShapes)
 template <typename T>
-int scan_fwd_dispatch(const oss_scan_fwd_params &p, int variant, int seg_req, hipStream_t stream) {
-    switch (variant) {
-        case 0: return launch_fwd<T, 64, 8, 8>(p, seg_req, stream);
-        case 1: return launch_fwd<T, 32, 16, 8>(p, seg_req, stream);
-        case 2: return launch_fwd<T, 16, 16, 4>(p, seg_req, stream);
-        case 3: return launch_fwd<T, 64, 16, 8>(p, seg_req, stream);
-        case 6: return launch_fwd<T, 64, 16, 12>(p, seg_req, stream);   // 12 rows per workgroup: one workgroup per CU at 3072 rows
-        default: return launch_fwd<T, 64, 4, 4>(p, seg_req, stream);
+int scan_fwd_dispatch(const oss_scan_fwd_params &p, const ScanFwdPlan &pl, hipStream_t stream) {
+    switch (pl.kernel.variant) {
+        case 0: return launch_fwd<T, 64, 8, 8>(p, pl, stream);
+        case 1: return launch_fwd<T, 32, 16, 8>(p, pl, stream);
+        case 2: return launch_fwd<T, 16, 16, 4>(p, pl, stream);
+        case 3: return launch_fwd<T, 64, 16, 8>(p, pl, stream);
+        case 6: return launch_fwd<T, 64, 16, 12>(p, pl, stream);   // 12 rows per workgroup: one workgroup per CU at 3072 rows
+        default: return launch_fwd<T, 64, 4, 4>(p, pl, stream);
     }
 }
 
-template int scan_fwd_dispatch<float>(const oss_scan_fwd_params &, int, int, hipStream_t);
-template int scan_fwd_dispatch<bf16_t>(const oss_scan_fwd_params &, int, int, hipStream_t);
-template int scan_fwd_dispatch<f16_t>(const oss_scan_fwd_params &, int, int, hipStream_t);
+template int scan_fwd_dispatch<float>(const oss_scan_fwd_params &, const ScanFwdPlan &, hipStream_t);
+template int scan_fwd_dispatch<bf16_t>(const oss_scan_fwd_params &, const ScanFwdPlan &, hipStream_t);
+template int scan_fwd_dispatch<f16_t>(const oss_scan_fwd_params &, const ScanFwdPlan &, hipStream_t);
 
 }  // namespace oss
