@@ -477,6 +477,11 @@ size_t oss_proj_wgrad_partial_floats(int batch, int D, int C, int R, int seqlen)
 /* 16-bit I/O runs oss_proj_fwd / _dgrad on the matrix cores (MFMA); float I/O, or force_vector_alu != 0
  * (tests, A-B timing), on the vector-ALU kernels.  Same results up to the summation order. */
 void oss_proj_set_path(int force_vector_alu);
+/* A-B switch of the dispatch inside oss_proj_fwd: with 16-bit I/O, dts != NULL, R <= 8, D % 16 == 0, D <= 192, seqlen a multiple of
+ * the 64- or 128-step tile and 16-byte aligned tensors, x_proj and dt_proj run as ONE launch (oss_proj_fwd_dt_kernel: the dt
+ * projection is an epilogue on the tile of xdbl still in LDS) -- bit-identical to the two launches.  on = 0 never takes it (the
+ * library starts with on = 1); on = 64 | 128 forces its tile width, 1 = by grid size */
+void oss_proj_set_one_launch(int on);
 /* 1 when oss_proj_fwd may be called with dts == NULL / oss_proj_dgrad with ddts == NULL at this shape (the matrix-core projection
  * kernels: 16-bit I/O, even seqlen, D <= 768, 2 C <= 256, R <= 32, and the vector-ALU path not forced) -- i.e. when the dt rows of
  * the gradient of x_dbl may come from somewhere else (oss_scan_bwd_params.finish_dt_weight, the fused-delta form) */
@@ -964,12 +969,12 @@ int oss_f32_matmul_modes(void);
  * compiled against another revision of this header would hand the kernels garbage pointers.  OSS_ABI_VERSION is bumped with
  * every change of a struct or of an entry point's argument list (9: the pre-packed weight images of the 1x1 convolutions,
  * oss_conv1x1_pack_* and the *_packed entry points; 10: oss_chan_params lost zt and dts, the channel kernels evaluate the
- * projections from the pooled vector); oss_abi_struct_bytes(which) is the library's own sizeof
+ * projections from the pooled vector; 11: the added entry point oss_proj_set_one_launch); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 10
+#define OSS_ABI_VERSION 11
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

@@ -533,6 +533,7 @@ int oss_proj_dgrad(oss_dtype io, const void *ddts, void *dxdbl, const void *du, 
 }
 
 void oss_proj_set_path(int force_vector_alu) { proj_force_valu(force_vector_alu); }
+void oss_proj_set_one_launch(int on) { proj_set_one_launch(on); }
 int oss_proj_rows_optional_ok(oss_dtype io, int batch, int D, int C, int R, int seqlen) {
     return proj_mfma_ok(io, batch, D, C, R, seqlen) ? 1 : 0;
 }

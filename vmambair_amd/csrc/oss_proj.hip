@@ -12,6 +12,8 @@
 // wave is 64 consecutive elements of one row, and no operand ever crosses lanes.  Output rows
 // (forward) / input rows (gradient) are dealt to the waves of the workgroup; nothing is reshaped into
 // a GEMM.  Weights are the fp32 master parameters; activations / gradients are the I/O type T.
+// (16-bit I/O runs on the matrix cores further down; where the shape allows, the forward is ONE launch for both products:
+// oss_proj_fwd_dt_kernel.)
 #include "oss_device.h"
 #include "oss_host.h"
 #include "oss_mfma.h"
@@ -356,6 +358,170 @@ oss_proj_fwd_mfma_kernel(const T *__restrict__ x2, const float *__restrict__ Wx,
                 *reinterpret_cast<uint32_t *>(xdbl + ((size_t)(b * 4 + j + 2 * k2) * C + (row - k2 * C)) * L + p) =
                     pack2<T>(acca[r], accb[r]);
             }
+        }
+    }
+}
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------------------------------------
+// Both forward products in ONE launch (16-bit I/O, R <= 8, D % 16 == 0, D <= 192, L % PT == 0, 16-byte aligned tensors): the dt
+// projection reads nothing but the R dt rows of the tile of xdbl its workgroup has just produced, so it runs as an epilogue on that
+// tile while it is still in LDS.  One workgroup of 4 waves = PT time steps of one flattening j, workgroup-level operand path as
+// oss_conv1x1_wg.hip:
+//   1. x2[b, j, 0..D, p0..p0+PT) -> LDS as it lies in memory (16-byte accesses); the 2 D R dt weights of directions j, j + 2 -> LDS
+//      (rows padded to 8, zeros past R);
+//   2. wave w computes the 32-row tiles w, w + 4, .. of the 2C rows over all PT steps: MFMA B fragments by ds_read_b64_tr_b16, the
+//      weight fragments as in oss_proj_fwd_mfma_kernel (fp32 master rows, cvt8<T>), k-steps ascending, channel k = 16 ks + 8 kg + e
+//      in the same operand slot -- every xdbl element is the same sequence of products into one accumulator as there;
+//   3. the results, rounded to T, go into the workgroup's LDS tile [row][step] and out to xdbl as 16-byte stores;
+//   4. dts[b, k, d, p] = sum_r Wdt[k, d, r] z[r, p] on the ROUNDED dt rows in that tile: a lane takes 8 consecutive steps, a wave
+//      one direction and every other group of 64 / (PT / 8) rows d; fmaf over r = 0 .. 7 ascending from 0 with zero weights and
+//      zero rows past R, exactly oss_dt_fwd_kernel<T, 8, V>'s sum; 16-byte stores.
+// KS: k-steps the instantiation is unrolled for (D <= 16 KS); PT: 128 | 64.  grid (L / PT, 2, B).
+// Dynamic LDS: T xs[D][PT + 32], T zs[32 mt_total][PT + 8], float wd[2 D][8].
+// ---------------------------------------------------------------------------------------------
+template <typename T, int KS, int PT>
+__global__ void __launch_bounds__(256)
+oss_proj_fwd_dt_kernel(const T *__restrict__ x2, const float *__restrict__ Wx, const float *__restrict__ Wdt, T *__restrict__ xdbl,
+                       T *__restrict__ dts, int D, int C, int R, int L) {
+    constexpr int NCT = PT / 32, PX = PT + 32, PITCH = PT + 8, CPR = PT / 8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char pd_smem[];
+    const int M = 2 * C, mt_total = (M + 31) >> 5, ksteps = D >> 4;
+    T *xs = reinterpret_cast<T *>(pd_smem);                                  // [D][PX]
+    T *zs = xs + D * PX;                                                     // [32 mt_total][PITCH]
+    float *wd = reinterpret_cast<float *>(zs + 32 * mt_total * PITCH);       // [2 D][8]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = blockIdx.y, b = blockIdx.z, p0 = blockIdx.x * PT;
+    const int col = lane & 31, kg = lane >> 5;
+    // weight fragments of row tile mt (A-operand row mt * 32 + col of this lane): one group of loads, clamped addresses
+    struct WRaw { f32x4 lo[KS], hi[KS]; };
+    auto issue = [&](int mt, WRaw &r) {
+        const int qc = min(mt * 32 + col, M - 1), kk = qc >= C ? 1 : 0;
+        const float *wrow = Wx + ((size_t)((j + 2 * kk) * C + (qc - kk * C))) * D;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int k0 = ks * 16 + kg * 8;
+            const float *wp = wrow + (k0 + 8 <= D ? k0 : 0);
+            r.lo[ks] = *reinterpret_cast<const f32x4 *>(wp);
+            r.hi[ks] = *reinterpret_cast<const f32x4 *>(wp + 4);
+        }
+    };
+    WRaw cur;
+    if (wave < mt_total) issue(wave, cur);   // in flight across the copies below
+    // the dt weights of the two directions, rows padded to 8: element i of thread tid is (row, r) = ((tid + 256 i) / 8, tid % 8)
+    {
+        float wv[KS];
+        const int r = tid & 7;
+#pragma unroll
+        for (int i = 0; i < KS; ++i) {
+            const int row = min((tid + 256 * i) >> 3, 2 * D - 1), kk = row >= D ? 1 : 0;
+            wv[i] = Wdt[((size_t)(j + 2 * kk) * D + (row - kk * D)) * R + min(r, R - 1)];
+        }
+#pragma unroll
+        for (int i = 0; i < KS; ++i)
+            if (tid + 256 * i < 16 * D) wd[tid + 256 * i] = r < R ? wv[i] : 0.f;
+    }
+    // 1. the activation tile, 16 bytes per lane: lane -> (channel, 8-step chunk), a row's chunks on consecutive lanes
+    {
+        const T *xb = x2 + ((size_t)(b * 2 + j) * D) * L + p0;
+        constexpr int NCP = (16 * KS * CPR + 255) / 256, GROUP = 6;
+        const int total = D * CPR;
+#pragma unroll
+        for (int i0 = 0; i0 < NCP; i0 += GROUP) {
+            u32x4 q[GROUP];
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) {
+                if (i0 + i < NCP) {
+                    const int idx = min(tid + (i0 + i) * 256, total - 1);
+                    const int c = idx / CPR, pc = idx - c * CPR;
+                    q[i] = *reinterpret_cast<const u32x4 *>(xb + (size_t)c * L + 8 * pc);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) {
+                if (i0 + i < NCP) {
+                    const int idx = tid + (i0 + i) * 256;
+                    const int c = idx / CPR, pc = idx - c * CPR;
+                    if (idx < total) *reinterpret_cast<u32x4 *>(xs + c * PX + 8 * pc) = q[i];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // 2. + 3.  (transpose-read addressing as in oss_conv1x1_wg_kernel: the lane then holds step i16 of its 16-lane group's block)
+    const int i16 = lane & 15, g = lane >> 4;
+    const int tr_off = (8 * (g >> 1) + (i16 >> 2)) * PX + 16 * (g & 1) + 4 * (i16 & 3);
+    for (int mt = wave; mt < mt_total; mt += 4) {
+        const int m0 = mt * 32;
+        const bool qok = m0 + col < M;
+        f32x16 acc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            if (ks < ksteps) {
+                const s16x8 af = qok ? cvt8<T>(cur.lo[ks], cur.hi[ks]) : s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+                    const T *bp = xs + ks * 16 * PX + ct * 32 + tr_off;
+                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(bp));
+                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(bp + 4 * PX));
+                    const s16x8 bf = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                    acc[ct] = Mfma<T>::run(af, bf, acc[ct]);
+                }
+            }
+        }
+        if (mt + 4 < mt_total) issue(mt + 4, cur);
+        T *ow = zs + m0 * PITCH;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * kg;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) ow[row * PITCH + ct * 32 + col] = from_f32<T>(acc[ct][r]);
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < 32 * CPR / 64; ++q) {
+            const int chunk = q * 64 + lane, row = chunk / CPR, pc = chunk - row * CPR;
+            const int qr = m0 + row;
+            if (qr < M) {
+                const int k2 = qr >= C ? 1 : 0;
+                *reinterpret_cast<u32x4 *>(xdbl + ((size_t)(b * 4 + j + 2 * k2) * C + (qr - k2 * C)) * L + p0 + 8 * pc) =
+                    *reinterpret_cast<const u32x4 *>(ow + row * PITCH + 8 * pc);
+            }
+        }
+    }
+    __syncthreads();
+    // 4. dt epilogue: wave -> direction kk = wave / 2; lane -> (row in the group of RPI, 8-step chunk)
+    {
+        constexpr int RPI = 64 / CPR;   // rows of dts per wave and pass
+        const int kk = wave >> 1, pc = lane % CPR, sub = lane / CPR;
+        float zr[8][8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const u32x4 q = *reinterpret_cast<const u32x4 *>(zs + (kk * C + min(r, R - 1)) * PITCH + 8 * pc);
+            unpack2<T>(q.x, zr[r][0], zr[r][1]); unpack2<T>(q.y, zr[r][2], zr[r][3]);
+            unpack2<T>(q.z, zr[r][4], zr[r][5]); unpack2<T>(q.w, zr[r][6], zr[r][7]);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) zr[r][i] = r < R ? zr[r][i] : 0.f;
+        }
+        const float *wk = wd + kk * D * 8;
+        T *ob = dts + ((size_t)(b * 4 + j + 2 * kk) * D) * L + p0 + 8 * pc;
+        for (int d = (wave & 1) * RPI + sub; d < D; d += 2 * RPI) {
+            const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wk + d * 8), w1 = *reinterpret_cast<const f32x4 *>(wk + d * 8 + 4);
+            const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            float s[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) s[i] = 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) s[i] = __builtin_fmaf(wv[r], zr[r][i], s[i]);
+            store_v<T, 8>(ob + (size_t)d * L, s);
         }
     }
 }
@@ -733,12 +899,55 @@ static int dt_waves(int B, int L, int D) {
     return nw;
 }
 
+// 0 = x_proj and dt_proj always as two launches (A-B timing: proj_set_one_launch); 1 = one launch where the shape allows, tile by
+// grid size; 64 | 128 = the same with that tile forced
+static std::atomic<int> g_proj_one_launch{1};
+void proj_set_one_launch(int on) { g_proj_one_launch.store(on == 64 || on == 128 ? on : (on ? 1 : 0)); }
+
+static size_t proj_fwd_dt_lds_bytes(int D, int C, int pt) {
+    return (size_t)D * 2 * (pt + 32) + (size_t)32 * ((2 * C + 31) / 32) * 2 * (pt + 8) + (size_t)2 * D * 8 * sizeof(float);
+}
+// time steps per workgroup of oss_proj_fwd_dt_kernel, 0 = the shape stays on the two launches.  128 while that still gives two
+// workgroups per CU, else 64.
+static int proj_fwd_dt_tile(const void *x2, const float *Wx, const float *Wdt, const void *xdbl, const void *dts, int B, int D, int C,
+                            int R, int L) {
+    const int mode = g_proj_one_launch.load();
+    if (!mode || !dts || R > 8 || D % 16 != 0 || D > 192 || L % 64 != 0) return 0;
+    if ((reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(xdbl) | reinterpret_cast<uintptr_t>(dts) |
+         reinterpret_cast<uintptr_t>(Wx) | reinterpret_cast<uintptr_t>(Wdt)) & 15u) return 0;
+    int pt = mode == 1 ? (L % 128 == 0 && 2L * B * (L / 128) >= 512 ? 128 : 64) : mode;
+    if (L % pt != 0) pt = 64;
+    return proj_fwd_dt_lds_bytes(D, C, pt) <= kMaxLdsBytes ? pt : 0;
+}
+
+template <typename T, int KS, int PT>
+static int proj_fwd_dt_launch(const T *x2, const float *Wx, const float *Wdt, T *xdbl, T *dts, int B, int D, int C, int R, int L,
+                              hipStream_t s) {
+    const size_t smem = proj_fwd_dt_lds_bytes(D, C, PT);
+    auto kern = oss_proj_fwd_dt_kernel<T, KS, PT>;
+    static LdsGate gate;
+    if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;
+    hipLaunchKernelGGL(kern, dim3(L / PT, 2, B), dim3(256), smem, s, x2, Wx, Wdt, xdbl, dts, D, C, R, L);
+    return (int)hipGetLastError();
+}
+
 template <typename T>
 static int proj_fwd_mfma_t(const void *x2, const float *Wx, const float *Wdt, void *xdbl, void *dts, int B, int D, int C, int R,
                            int L, hipStream_t s) {
     const T *xp = reinterpret_cast<const T *>(x2);
     T *zp = reinterpret_cast<T *>(xdbl), *dp = reinterpret_cast<T *>(dts);
-    const int mt = (2 * C + 31) / 32, per = mfma_tiles_per_wg(B, L, mt), splits = (mt + per - 1) / per;
+    if (const int pt = proj_fwd_dt_tile(x2, Wx, Wdt, xdbl, dts, B, D, C, R, L)) {
+        const int ks1 = D / 16;
+        if (pt == 128) {
+            if (ks1 <= 3)      return proj_fwd_dt_launch<T, 3, 128>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+            else if (ks1 <= 6) return proj_fwd_dt_launch<T, 6, 128>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+            else               return proj_fwd_dt_launch<T, 12, 128>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+        }
+        if (ks1 <= 3)      return proj_fwd_dt_launch<T, 3, 64>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+        else if (ks1 <= 6) return proj_fwd_dt_launch<T, 6, 64>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+        else               return proj_fwd_dt_launch<T, 12, 64>(xp, Wx, Wdt, zp, dp, B, D, C, R, L, s);
+    }
+    const int mt =(2 * C + 31) / 32, per = mfma_tiles_per_wg(B, L, mt), splits = (mt + per - 1) / per;
     dim3 grid((L + 255) / 256, 2 * splits, B);
     const int ks = (D + 15) / 16;
     if (ks <= 3)       hipLaunchKernelGGL((oss_proj_fwd_mfma_kernel<T, 3>), grid, dim3(256), 0, s, xp, Wx, zp, D, C, L, per);   // d_inner 48: no duplicate k-steps
