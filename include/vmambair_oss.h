@@ -840,6 +840,33 @@ size_t oss_usm_scratch_floats(int64_t batch, int64_t channels, int64_t h, int64_
 int oss_usm_sharp(const float *img, const float *g, float *out, float *mask, float *scratch, int64_t batch, int64_t channels,
                   int64_t h, int64_t w, int k, float weight, float threshold, oss_stream_t stream);
 
+/* DiffJPEG, the JPEG step of the same pipeline (oss_jpeg.hip; MambaRealSR_model.py:189-191, :234-241; basicsr.utils.diffjpeg), as
+ * one launch: img (batch, 3, h, w) dense fp32 in [0, 1] -> out of the same shape, which must not overlap img.
+ *   factor     per sample: (q < 50 ? 5000 / q : 200 - 2 q) / 100 in fp32.  quality != NULL: q = quality[b], batch fp32 values in
+ *              DEVICE memory that the kernel reads (no host read, so a captured launch follows later writes to them);
+ *              quality == NULL: q = quality_scalar for every sample, converted on the host.  q = 100 gives factor 0 and NaN output,
+ *              as in the package.
+ *   compress   zero padding at the bottom and right to H, W = multiples of 16 (inside the load); p = 255 x; Y, Cb, Cr with the
+ *              package's fp32 matrix; Cb, Cr averaged over 2 x 2; per 8 x 8 block F = DCT-II(block - 128), orthonormal;
+ *              c = rint(F / (T * factor)) with round-half-even, T = the luminance table transposed / the chrominance table
+ *   decompress c * (T * factor), inverse DCT, + 128, Cb and Cr replicated 2 x 2, the package's inverse matrix, clamp to [0, 255],
+ *              * fp32(1 / 255) (torch's division of a device tensor by 255), cropped to h x w by guarded stores
+ *   flags      OSS_JPEG_CLAMP_INPUT: x is clamped to [0, 1] first (:190, :235, :240); OSS_JPEG_QUANTISE: the epilogue
+ *              clamp(rint(x * 255), 0, 255) / 255 of :248, with the bits of OSS_FILTER_QUANTISE; OSS_JPEG_DIFF_ROUND:
+ *              c = rint(v) + (v - rint(v))^3, the package's differentiable rounding (the forward value only: no backward exists)
+ *   coef_y, coef_cb, coef_cr   each may be NULL (nothing is written): the quantised coefficients c as fp32 in the layout of
+ *              basicsr's CompressJpeg, (batch, H W / 64, 8, 8) and twice (batch, H W / 256, 8, 8), blocks row-major over the
+ *              padded plane, [u][v] = [vertical][horizontal] frequency
+ * Nothing is allocated or read back.  oss_jpeg_workgroups is a pure host call and the support query: 0 for a dimension < 1 or
+ * above 2^24 or more than 2^31 - 1 macroblocks (16 x 16).  oss_jpeg_roundtrip returns OSS_ERR_SHAPE for the same and for an unknown
+ * flag, OSS_ERR_NULL when img or out is missing, without a launch. */
+#define OSS_JPEG_CLAMP_INPUT 1
+#define OSS_JPEG_QUANTISE 2
+#define OSS_JPEG_DIFF_ROUND 4
+size_t oss_jpeg_workgroups(int64_t batch, int64_t h, int64_t w);
+int oss_jpeg_roundtrip(const float *img, const float *quality, float quality_scalar, float *out, float *coef_y, float *coef_cb,
+                       float *coef_cr, int64_t batch, int64_t h, int64_t w, int flags, oss_stream_t stream);
+
 /* The reference's pixel losses with their gradients on the device (oss_pixel_loss.hip): L1Loss, MSELoss, PSNRLoss (with toY) and
  * CharbonnierLoss of Deraining/basicsr/models/losses/losses.py:26-122 with the weighting and reduction of weight_reduce_loss
  * (losses/loss_util.py:25-54).  lw = loss_weight, d = pred - target, n = batch * channels * plane:
@@ -969,12 +996,13 @@ int oss_f32_matmul_modes(void);
  * compiled against another revision of this header would hand the kernels garbage pointers.  OSS_ABI_VERSION is bumped with
  * every change of a struct or of an entry point's argument list (9: the pre-packed weight images of the 1x1 convolutions,
  * oss_conv1x1_pack_* and the *_packed entry points; 10: oss_chan_params lost zt and dts, the channel kernels evaluate the
- * projections from the pooled vector; 11: the added entry point oss_proj_set_one_launch); oss_abi_struct_bytes(which) is the library's own sizeof
+ * projections from the pooled vector; 11: the added entry point oss_proj_set_one_launch; 12: the added
+ * entry points oss_jpeg_workgroups and oss_jpeg_roundtrip); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 11
+#define OSS_ABI_VERSION 12
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

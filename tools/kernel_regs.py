@@ -28,7 +28,9 @@ def main():
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-S", "--cuda-device-only", *defs,
                            os.path.join(ROOT, "vmambair_amd", "csrc", tu + ".hip"), "-o", asm], stderr=subprocess.DEVNULL)
     txt = open(asm).read().split("\n")
+    funcs = {m.group(1) for m in (re.match(r"\s*\.type\s+(_Z\w+),@function", l) for l in txt) if m}   # not the __constant__ tables
     names = [(i, re.match(r"^(_Z\w+):", l).group(1)) for i, l in enumerate(txt) if re.match(r"^(_Z\w+):", l)]
+    names = [(i, n) for i, n in names if n in funcs]
     dem = subprocess.run(["c++filt"], input="\n".join(n for _, n in names), capture_output=True, text=True).stdout.split("\n")
     for (i, _), name in zip(names, dem):
         if pats and not any(p in name for p in pats):

@@ -815,6 +815,14 @@ int oss_usm_sharp(const float *img, const float *g, float *out, float *mask, flo
     return usm_sharp(img, g, out, mask, scratch, batch, channels, h, w, k, weight, threshold, reinterpret_cast<hipStream_t>(stream));
 }
 
+size_t oss_jpeg_workgroups(int64_t batch, int64_t h, int64_t w) { return jpeg_workgroups(batch, h, w); }
+int oss_jpeg_roundtrip(const float *img, const float *quality, float quality_scalar, float *out, float *coef_y, float *coef_cb,
+                       float *coef_cr, int64_t batch, int64_t h, int64_t w, int flags, oss_stream_t stream) {
+    if (!img || !out) return OSS_ERR_NULL;   // quality and the three coefficient outputs are optional
+    return jpeg_roundtrip(img, quality, quality_scalar, out, coef_y, coef_cb, coef_cr, batch, h, w, flags,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
 size_t oss_pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t batch, int64_t channels,
                                       int64_t plane) {
     return pixel_loss_partial_doubles(kind, flags, pred_io, target_io, batch, channels, plane);

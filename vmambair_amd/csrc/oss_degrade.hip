@@ -29,6 +29,7 @@
 // 4 k taps per pixel where the dense form has 2 k^2.
 #include <cmath>
 #include "oss_host.h"
+#include "oss_pixel_stage.h"
 
 namespace oss {
 
@@ -52,19 +53,9 @@ struct F2Args {
     int C, H, W, k, tilesX, tilesY, per_sample, epilogue;
 };
 
-// torch divides a device tensor by a Python scalar as a multiplication by the scalar's reciprocal, formed in double and rounded to
-// the tensor's type (BinaryDivTrueKernel.cu); ":248" on the device is therefore q * fp32(1 / 255), one unit in the last place from
-// the true quotient at some of the 256 levels
-constexpr float kInv255 = (float)(1.0 / 255.0);
-
-// torch's clamp gives +0 for -0 and for everything below 0; the "+ 0.0f" makes that independent of the max instruction's operand order
 __device__ __forceinline__ float f2_epilogue(float v, int epilogue) {
-#pragma clang fp contract(off)
-    if (epilogue == OSS_FILTER_CLAMP) return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f) + 0.0f;
-    if (epilogue == OSS_FILTER_QUANTISE) {
-        const float r = rintf(v * 255.0f);
-        return (r != r ? r : fminf(fmaxf(r, 0.0f), 255.0f) + 0.0f) * kInv255;
-    }
+    if (epilogue == OSS_FILTER_CLAMP) return clamp_unit(v);
+    if (epilogue == OSS_FILTER_QUANTISE) return quantise_255(v);
     return v;
 }
 

@@ -217,6 +217,10 @@ int filter_sep(const float *img, const float *g, float *out, float *scratch, int
 size_t usm_scratch_floats(int64_t B, int64_t C, int64_t H, int64_t W, int k);
 int usm_sharp(const float *img, const float *g, float *out, float *mask, float *scratch, int64_t B, int64_t C, int64_t H, int64_t W,
               int k, float weight, float threshold, hipStream_t s);
+// DiffJPEG of the same pipeline in one launch (oss_jpeg.hip); quality == nullptr: quality_scalar for every sample
+size_t jpeg_workgroups(int64_t B, int64_t h, int64_t w);
+int jpeg_roundtrip(const float *img, const float *quality, float quality_scalar, float *out, float *coef_y, float *coef_cb,
+                   float *coef_cr, int64_t B, int64_t h, int64_t w, int flags, hipStream_t s);
 // pixel losses with their gradients (oss_pixel_loss.hip); N, C, plane = batch, channels, H * W
 size_t pixel_loss_partial_doubles(int kind, int flags, oss_dtype pred_io, oss_dtype target_io, int64_t N, int64_t C, int64_t plane);
 size_t pixel_loss_stat_doubles(int kind, int flags, int64_t N, int64_t C, int64_t plane);

@@ -4,12 +4,14 @@ every training step (RealSR/VmambaIR/models/MambaRealSR_model.py:146-263):
   ``filter2D(img, kernel)``         a different 21 x 21 blur or sinc kernel per sample after reflect padding (:165, :196, :232/245)
   ``USMSharp(radius=50, sigma=0)``  unsharp masking of the ground truth with a 51 x 51 Gaussian (:154-155, :262)
   ``gaussian_kernel1d(k, sigma)``   the Gaussian vector ``USMSharp`` is built from
+  ``DiffJPEG(differentiable)``      JPEG compression and decompression with a quality per sample (:86, :189-191, :234-241)
   ``TrainingPairPool(queue_size)``  the training pair pool ``_dequeue_and_enqueue`` (:109-144)
 
-The reference imports ``filter2D`` and ``USMSharp`` from the pip ``basicsr`` package (``basicsr.utils``,
-``basicsr.utils.img_process_util``), which is not part of the reference tree.  Their definitions are restated here from that package's
-published source, and every test is anchored to an independent float64 evaluation of these formulas
-(``scipy.ndimage.correlate(..., mode='mirror')``, tests/golden/make_golden_degrade.py), not to reference code.  The pair pool is in the
+The reference imports ``filter2D``, ``USMSharp`` and ``DiffJPEG`` from the pip ``basicsr`` package (``basicsr.utils``,
+``basicsr.utils.img_process_util``, ``basicsr.utils.diffjpeg``), which is not part of the reference tree.  Their definitions are
+restated here from that package's published source, and every test is anchored to an independent float64 evaluation of these formulas
+(``scipy.ndimage.correlate(..., mode='mirror')``, tests/golden/make_golden_degrade.py; ``scipy.fft.dctn`` per 8 x 8 block,
+tests/golden/make_golden_jpeg.py), not to reference code.  The pair pool is in the
 reference tree; its fixture is a trace of the reference's own method.
 
 fp32 device tensors go to the HIP kernels of ``csrc/oss_degrade.hip`` (``torch.ops.vmambair.filter2d`` / ``usm_sharp``):
@@ -18,11 +20,15 @@ quantisation ``clamp((x * 255).round(), 0, 255) / 255`` (:248) as the kernel's l
 the 51-vector it built itself (4 k taps per pixel where the dense form has 2 k^2).  Nothing in ``feed_data`` is differentiated, so no
 backward exists: the device paths run under ``torch.no_grad`` and return tensors without a graph.  A plain-torch restatement serves
 CPU tensors, non-fp32 input, k above the kernels' limits and, in ``filter2D``, a large (1, k, k) kernel, which need not be rank 1 -- as
-``losses.py`` and ``metrics.py`` do for CPU inputs.  ``DiffJPEG``, the other operator of ``feed_data`` that lives in ``basicsr``, is
-not here.
+``losses.py`` and ``metrics.py`` do for CPU inputs.  ``DiffJPEG`` on a contiguous fp32 device tensor is one launch of
+``csrc/oss_jpeg.hip`` (``torch.ops.vmambair.jpeg_roundtrip``) per call, with the quality of every sample read on the device; its
+restatement ``restate_diffjpeg`` follows the package operation by operation.  What is left of ``feed_data`` -- ``F.interpolate`` and
+the two noise functions -- is plain torch.
 """
 from __future__ import annotations
 
+import functools
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -71,6 +77,106 @@ def restate_usm(img: torch.Tensor, kernel: torch.Tensor, weight: float = 0.5, th
     soft_mask = restate_filter2d(mask, kernel)
     sharp = torch.clip(img + weight * residual, 0, 1)
     return soft_mask * sharp + (1 - soft_mask) * img
+
+
+# basicsr.utils.diffjpeg: the luminance table is the standard one TRANSPOSED (the package transposes it when it builds the parameter),
+# the chrominance table is 99 outside its symmetric top-left 4 x 4 block; all matrices are float32 constants in the package
+_JPEG_Y_TABLE = ((16, 11, 10, 16, 24, 40, 51, 61), (12, 12, 14, 19, 26, 58, 60, 55), (14, 13, 16, 24, 40, 57, 69, 56),
+                 (14, 17, 22, 29, 51, 87, 80, 62), (18, 22, 37, 56, 68, 109, 103, 77), (24, 35, 55, 64, 81, 104, 113, 92),
+                 (49, 64, 78, 87, 103, 121, 120, 101), (72, 92, 95, 98, 112, 100, 103, 99))
+_JPEG_C_BLOCK = ((17, 18, 24, 47), (18, 21, 26, 66), (24, 26, 56, 99), (47, 66, 99, 99))
+_JPEG_RGB2YCC = ((0.299, 0.587, 0.114), (-0.168736, -0.331264, 0.5), (0.5, -0.418688, -0.081312))
+_JPEG_YCC2RGB = ((1., 0., 1.402), (1., -0.344136, -0.714136), (1., 1.772, 0.))
+
+
+@functools.lru_cache(maxsize=None)
+def _jpeg_constants(dtype: torch.dtype, device: torch.device):
+    f32 = functools.partial(torch.tensor, dtype=torch.float32)
+    y_table = f32(_JPEG_Y_TABLE).t().contiguous()
+    c_table = torch.full((8, 8), 99., dtype=torch.float32)
+    c_table[:4, :4] = f32(_JPEG_C_BLOCK).t()
+    n = torch.arange(8, dtype=torch.float64)
+    cos = torch.cos((2 * n[:, None] + 1) * n[None, :] * math.pi / 16)            # [x][u]
+    dct = cos[:, None, :, None] * cos[None, :, None, :]                           # [x][y][u][v]
+    alpha = torch.tensor([1. / math.sqrt(2)] + [1.] * 7, dtype=torch.float64)
+    alpha = torch.outer(alpha, alpha)
+    out = dict(y_table=y_table, c_table=c_table, rgb2ycc=f32(_JPEG_RGB2YCC).t(), ycc2rgb=f32(_JPEG_YCC2RGB).t(),
+               shift=f32([0., 128., 128.]), unshift=f32([0., -128., -128.]), dct=dct, idct=dct.permute(2, 3, 0, 1).contiguous(),
+               scale=alpha * 0.25, alpha=alpha)
+    return {k: v.to(device=device, dtype=dtype) for k, v in out.items()}
+
+
+def quality_to_factor(quality):
+    """basicsr.utils.diffjpeg.quality_to_factor, on a Python number or a 0-dim tensor (then ``if`` reads the value on the host)"""
+    if quality < 50:
+        quality = 5000. / quality
+    else:
+        quality = 200. - quality * 2
+    return quality / 100.
+
+
+def _jpeg_blocks(plane: torch.Tensor) -> torch.Tensor:
+    """(B, H, W) -> (B, H W / 64, 8, 8), blocks row-major"""
+    b = plane.size(0)
+    return plane.view(b, plane.size(1) // 8, 8, -1, 8).permute(0, 1, 3, 2, 4).contiguous().view(b, -1, 8, 8)
+
+
+def _jpeg_merge(blocks: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    b = blocks.size(0)
+    return blocks.view(b, height // 8, width // 8, 8, 8).permute(0, 1, 3, 2, 4).contiguous().view(b, height, width)
+
+
+def _jpeg_round(v: torch.Tensor, differentiable: bool) -> torch.Tensor:
+    r = torch.round(v)
+    return r + (v - r) ** 3 if differentiable else r
+
+
+def _restate_jpeg_from_factor(x: torch.Tensor, factor, differentiable: bool):
+    """``factor``: a Python number or a (B,) tensor of x's dtype -> (out, (y, cb, cr)), operation by operation as the package"""
+    if x.dim() != 4 or x.size(1) != 3:
+        raise ValueError(f"DiffJPEG: x must be (B, 3, h, w), not {tuple(x.shape)}")
+    k = _jpeg_constants(x.dtype, x.device)
+    b, _, h, w = x.size()
+    x = F.pad(x, (0, -w % 16, 0, -h % 16), mode='constant', value=0)
+    height, width = x.size()[-2:]
+    if torch.is_tensor(factor):
+        factor = factor.view(b, 1, 1, 1)
+    # CompressJpeg: rgb2ycbcr_jpeg, chroma_subsampling, block_splitting, dct_8x8, y_quantize / c_quantize
+    ycc = torch.tensordot((x * 255).permute(0, 2, 3, 1), k['rgb2ycc'], dims=1) + k['shift']
+    planes = ycc.permute(0, 3, 1, 2).clone()
+    cb = F.avg_pool2d(planes[:, 1:2], kernel_size=2, stride=(2, 2), count_include_pad=False).squeeze(1)
+    cr = F.avg_pool2d(planes[:, 2:3], kernel_size=2, stride=(2, 2), count_include_pad=False).squeeze(1)
+    coef, tables = [], []
+    for plane, table in ((ycc[..., 0], k['y_table']), (cb, k['c_table']), (cr, k['c_table'])):
+        freq = k['scale'] * torch.tensordot(_jpeg_blocks(plane) - 128, k['dct'], dims=2)
+        tables.append(table.expand(b, 1, 8, 8) * factor)
+        coef.append(_jpeg_round(freq / tables[-1], differentiable))
+    # DeCompressJpeg: dequantize, idct_8x8, block_merging, chroma_upsampling, ycbcr2rgb_jpeg
+    rec = []
+    for c, table, (hh, ww) in zip(coef, tables, ((height, width), (height // 2, width // 2), (height // 2, width // 2))):
+        rec.append(_jpeg_merge(0.25 * torch.tensordot(c * table * k['alpha'], k['idct'], dims=2) + 128, hh, ww))
+    up = [p.unsqueeze(-1).repeat(1, 1, 2, 2).view(-1, height, width) for p in rec[1:]]
+    image = torch.stack([rec[0], up[0], up[1]], dim=3)
+    image = torch.tensordot(image + k['unshift'], k['ycc2rgb'], dims=1).permute(0, 3, 1, 2)
+    image = torch.min(255 * torch.ones_like(image), torch.max(torch.zeros_like(image), image))
+    return (image / 255)[:, :, 0:h, 0:w], tuple(coef)
+
+
+def _restate_jpeg(x: torch.Tensor, quality, differentiable: bool):
+    if torch.is_tensor(quality):
+        if quality.dim() != 1 or quality.numel() != x.size(0):
+            raise ValueError(f"DiffJPEG: quality must be a number or a (B,) tensor, not {tuple(quality.shape)}")
+        q = quality.to(device=x.device, dtype=x.dtype)
+        factor = torch.where(q < 50, 5000. / q, 200. - q * 2) / 100.   # the package loops over the samples on the host
+    else:
+        factor = quality_to_factor(quality)
+    return _restate_jpeg_from_factor(x, factor, differentiable)
+
+
+def restate_diffjpeg(x: torch.Tensor, quality, differentiable: bool = False) -> torch.Tensor:
+    """basicsr.utils.diffjpeg.DiffJPEG.forward for ``x`` (B, 3, h, w) in [0, 1] and ``quality`` a Python number or a (B,) tensor,
+    which is left as it is"""
+    return _restate_jpeg(x, quality, differentiable)[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -147,6 +253,57 @@ class USMSharp(nn.Module):
             with torch.no_grad():
                 return _ops.usm_sharp(img.contiguous(), self._g, float(weight), float(threshold), False)[0]
         return restate_usm(img, self.kernel, weight, threshold)
+
+
+class DiffJPEG(nn.Module):
+    """basicsr.utils.diffjpeg.DiffJPEG: ``forward(x, quality)`` compresses ``x`` (B, 3, h, w) in [0, 1] to quantised DCT coefficients
+    and decompresses them again; ``quality`` is a Python number or a (B,) tensor, one quality per sample.  The reference's
+    ``DiffJPEG(differentiable=False).cuda()(out, quality=jpeg_p)`` (MambaRealSR_model.py:86, :189-191, :234-241) works unchanged::
+
+        factor = (5000 / q if q < 50 else 200 - 2 q) / 100              pad bottom and right with zeros to multiples of 16
+        Y, Cb, Cr = M (255 x) + (0, 128, 128)                            Cb, Cr averaged over 2 x 2
+        per 8 x 8 block:  F = DCT-II(block - 128), orthonormal;  c = round(F / (T factor));  block' = IDCT(c T factor) + 128
+        Cb', Cr' replicated 2 x 2;  out = clamp(M' (Y', Cb' - 128, Cr' - 128), 0, 255) / 255, cropped to h x w
+
+    with ``T`` the luminance table transposed (as the package holds it) or the chrominance table, and round-half-even.
+    ``differentiable=True`` (the package's default) replaces ``round(v)`` by ``round(v) + (v - round(v))^3``.
+
+    A contiguous fp32 device tensor is one launch of ``csrc/oss_jpeg.hip`` (``torch.ops.vmambair.jpeg_roundtrip``) without a graph.
+    Keyword-only extras, stages of that launch: ``clamp_input`` clamps ``x`` to [0, 1] first (:190, :235, :240), ``quantise``
+    applies ``clamp((out * 255).round(), 0, 255) / 255`` (:248) last, ``return_coefficients`` returns ``(out, (y, cb, cr))`` with
+    the quantised coefficients in the layout of the package's ``CompressJpeg``: ``y`` (B, H W / 64, 8, 8), ``cb`` and ``cr``
+    (B, H W / 256, 8, 8) for the padded H x W.  ``restate_diffjpeg``, plain torch, serves CPU tensors, other dtypes, non-contiguous
+    views, shapes the kernel refuses, and every call that can carry a gradient: ``differentiable=True`` with gradients enabled, or
+    an ``x`` that requires one.  ``C != 3`` raises ``ValueError``.
+
+    Deviations from the package: the caller's ``quality`` tensor is left unchanged (the package overwrites it in place with the
+    factors); nothing is read back to the host (the package's loop ``for i in range(B): factor[i] = quality_to_factor(factor[i])``
+    reads B device scalars), so a call can be captured into a graph and replayed with other qualities.  ``quality = 100`` gives
+    factor 0 and NaN, as in the package."""
+
+    def __init__(self, differentiable: bool = True):
+        super().__init__()
+        self.differentiable = bool(differentiable)
+
+    def forward(self, x: torch.Tensor, quality, *, clamp_input: bool = False, quantise: bool = False,
+                return_coefficients: bool = False):
+        if x.dim() != 4 or x.size(1) != 3:
+            raise ValueError(f"DiffJPEG: x must be (B, 3, h, w), not {tuple(x.shape)}")
+        per_sample = torch.is_tensor(quality)
+        if per_sample and (quality.dim() != 1 or quality.numel() != x.size(0)):
+            raise ValueError(f"DiffJPEG: quality must be a number or a (B,) tensor, not {tuple(quality.shape)}")
+        carries_grad = torch.is_grad_enabled() and (self.differentiable or x.requires_grad)
+        if not carries_grad and x.is_contiguous() and _ops.jpeg_ok(x):
+            flags = ((_ops.degrade.JPEG_CLAMP_INPUT if clamp_input else 0) | (_ops.degrade.JPEG_QUANTISE if quantise else 0)
+                     | (_ops.degrade.JPEG_DIFF_ROUND if self.differentiable else 0))
+            q = quality.detach().to(device=x.device, dtype=torch.float32).contiguous() if per_sample else None
+            with torch.no_grad():
+                out, y, cb, cr = _ops.jpeg_roundtrip(x, q, 0.0 if per_sample else float(quality), flags, return_coefficients)
+            return (out, (y, cb, cr)) if return_coefficients else out
+        out, coef = _restate_jpeg(torch.clamp(x, 0, 1) if clamp_input else x, quality, self.differentiable)
+        if quantise:
+            out = restate_quantise(out)
+        return (out, coef) if return_coefficients else out
 
 
 class TrainingPairPool:

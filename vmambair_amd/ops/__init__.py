@@ -11,7 +11,8 @@ One module per operator family (round 1 had a single 1 000-line ``ops.py``):
   ``dwconv``    depth-wise 3x3 (+ silu)          ``layernorm``  NCHW LayerNorm (+ gate)          ``ffn``  gelu gate of the EFFN
   ``metrics``   validation PSNR + SSIM of a batch of image pairs in one call (mean squared error, mean SSIM; fp64 on the device); the
                 features of the no-reference NIQE per 96 x 96 block of a batch of images
-  ``degrade``   filter2D (a k x k kernel per sample, reflect padded) and USM sharpening of the RealSR degradation pipeline, fp32
+  ``degrade``   filter2D (a k x k kernel per sample, reflect padded), USM sharpening and the JPEG round trip (DiffJPEG, one launch) of the
+                RealSR degradation pipeline, fp32
   ``losses``    the pixel losses (L1, MSE, Charbonnier, PSNR) with their gradient w.r.t. the prediction: fp64 sums in a fixed order
   ``pairs``     training batches cut from a device-resident pool of image pairs: counter-based draw + one crop / flip / convert launch
   ``_common``   dtype table, checks, deferred finishing, weight-gradient side stream
@@ -39,7 +40,7 @@ from .conv3x3 import DenseConv3x3Fn, conv3x3_dense_bwd, conv3x3_dense_fwd, dense
 from .conv3x3 import conv3x3 as conv3x3_layer  # noqa: F401
 from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gate, gelu_gate_bwd, gelu_gate_fwd  # noqa: F401
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401
-from .degrade import filter2d, filter2d_ok, filter_sep, filter_sep_ok, usm_sharp  # noqa: F401
+from .degrade import filter2d, filter2d_ok, filter_sep, filter_sep_ok, jpeg_ok, jpeg_roundtrip, usm_sharp  # noqa: F401
 from .losses import pixel_loss_bwd, pixel_loss_fwd, pixel_loss_ok  # noqa: F401
 from .metrics import image_metrics, image_metrics_ok, niqe_features, niqe_features_ok  # noqa: F401
 from .pairs import pairs_draw, pairs_draw_window, pairs_gather, pairs_gather_padded, pairs_ok  # noqa: F401

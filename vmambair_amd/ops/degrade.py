@@ -1,10 +1,11 @@
 """The degradation filters on the device: ``torch.ops.vmambair.filter2d`` / ``filter_sep`` / ``usm_sharp`` on ``oss_degrade.hip`` --
-``filter2D`` and ``USMSharp`` as ``MambaRealSR.feed_data`` calls them (RealSR/VmambaIR/models/MambaRealSR_model.py:146-263).
+``filter2D`` and ``USMSharp`` as ``MambaRealSR.feed_data`` calls them (RealSR/VmambaIR/models/MambaRealSR_model.py:146-263) -- and
+``torch.ops.vmambair.jpeg_roundtrip`` on ``oss_jpeg.hip``, the ``DiffJPEG`` of the same method in one launch.
 ``vmambair_amd.degradations`` is the public face; semantics and limits as in include/vmambair_oss.h.  fp32 only, nothing is
 differentiated."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -13,6 +14,7 @@ from ._common import _LIB, _check
 
 NONE, CLAMP, QUANTISE = (_capi.FILTER[k] for k in ("NONE", "CLAMP", "QUANTISE"))
 FILTER2D_MAX_K, FILTER_SEP_MAX_K = _capi.FILTER["2D_MAX_K"], _capi.FILTER["SEP_MAX_K"]
+JPEG_CLAMP_INPUT, JPEG_QUANTISE, JPEG_DIFF_ROUND = (_capi.JPEG[k] for k in ("CLAMP_INPUT", "QUANTISE", "DIFF_ROUND"))
 
 
 def _is_f32_image(img: torch.Tensor) -> bool:
@@ -102,9 +104,47 @@ def usm_sharp(img: torch.Tensor, g: torch.Tensor, weight: float, threshold: floa
     return out, mask
 
 
+def jpeg_ok(img: torch.Tensor) -> bool:
+    """whether the JPEG kernel takes this (B, 3, h, w) image (a host query of the library)"""
+    return _is_f32_image(img) and img.size(1) == 3 and _capi.load().oss_jpeg_workgroups(img.size(0), img.size(2), img.size(3)) > 0
+
+
+def jpeg_roundtrip(img: torch.Tensor, quality: Optional[torch.Tensor], quality_scalar: float, flags: int,
+                   want_coefficients: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (out, y, cb, cr): JPEG compression and decompression of ``img`` (B, 3, h, w) in [0, 1] as basicsr's ``DiffJPEG`` defines
+    them, with the quality of sample b read from ``quality`` (B,) on the device, or ``quality_scalar`` for all when ``quality`` is
+    None.  ``flags``: JPEG_CLAMP_INPUT | JPEG_QUANTISE | JPEG_DIFF_ROUND.  ``y`` (B, H W / 64, 8, 8), ``cb``, ``cr`` (B, H W / 256, 8, 8)
+    are the quantised coefficients of the image padded to H, W = multiples of 16 when ``want_coefficients``, empty tensors
+    otherwise.  One launch on the current stream, no host synchronisation."""
+    _checked_image("jpeg_roundtrip", img)
+    B, C, h, w = img.shape
+    _check(C == 3, "jpeg_roundtrip: img must have 3 channels")
+    if quality is not None:
+        _check(quality.is_cuda and quality.device == img.device and quality.dtype == torch.float32 and quality.dim() == 1
+               and quality.numel() == B and quality.is_contiguous(),
+               "jpeg_roundtrip: quality must be a contiguous fp32 (B,) tensor on img's device")
+    lib = _capi.load()
+    _check(lib.oss_jpeg_workgroups(B, h, w) > 0, f"jpeg_roundtrip: a {tuple(img.shape)} image is not supported")
+    _check(0 <= int(flags) <= JPEG_CLAMP_INPUT | JPEG_QUANTISE | JPEG_DIFF_ROUND, f"jpeg_roundtrip: unknown flags {flags}")
+    out = torch.empty_like(img)
+    if want_coefficients:
+        blocks = ((h + 15) // 16) * ((w + 15) // 16)
+        y, cb, cr = img.new_empty(B, 4 * blocks, 8, 8), img.new_empty(B, blocks, 8, 8), img.new_empty(B, blocks, 8, 8)
+    else:
+        y, cb, cr = img.new_empty(0), img.new_empty(0), img.new_empty(0)
+    with torch.cuda.device(img.device):
+        _capi.check(lib.oss_jpeg_roundtrip(img.data_ptr(), None if quality is None else quality.data_ptr(), float(quality_scalar),
+                                           out.data_ptr(), *((t.data_ptr() if want_coefficients else None) for t in (y, cb, cr)),
+                                           B, h, w, int(flags), torch.cuda.current_stream().cuda_stream), "oss_jpeg_roundtrip")
+    return out, y, cb, cr
+
+
 _LIB.define("filter2d(Tensor img, Tensor kernel, int epilogue) -> Tensor")
 _LIB.impl("filter2d", filter2d, "CUDA")
 _LIB.define("filter_sep(Tensor img, Tensor g) -> Tensor")
 _LIB.impl("filter_sep", filter_sep, "CUDA")
 _LIB.define("usm_sharp(Tensor img, Tensor g, float weight, float threshold, bool want_mask) -> (Tensor, Tensor)")
 _LIB.impl("usm_sharp", usm_sharp, "CUDA")
+_LIB.define("jpeg_roundtrip(Tensor img, Tensor? quality, float quality_scalar, int flags, bool want_coefficients) -> "
+            "(Tensor, Tensor, Tensor, Tensor)")
+_LIB.impl("jpeg_roundtrip", jpeg_roundtrip, "CUDA")
