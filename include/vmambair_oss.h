@@ -867,6 +867,76 @@ size_t oss_jpeg_workgroups(int64_t batch, int64_t h, int64_t w);
 int oss_jpeg_roundtrip(const float *img, const float *quality, float quality_scalar, float *out, float *coef_y, float *coef_cb,
                        float *coef_cr, int64_t batch, int64_t h, int64_t w, int flags, oss_stream_t stream);
 
+/* The two noise steps of the same pipeline (oss_noise.hip; MambaRealSR_model.py:177-187, :209-219; basicsr.data.degradations:
+ * generate_ / add_ / random_generate_ / random_add_ gaussian_noise_pt and poisson_noise_pt), without a host read.  img, out: dense
+ * fp32 (batch, channels, h, w); out must not be img.  Per element, in fp32 and in the package's operation order:
+ *   Gaussian  noise = (n_c * sigma_b / 255) * (1 - g_b) + (n_g[y, x] * sigma_b / 255) * g_b, n_c standard normal per element, n_g ONE
+ *             (h, w) standard normal field shared by all samples and channels, as in the package
+ *   Poisson   (channels == 3) q = clamp(rint(255 x), 0, 255) / 255; vals_b = the next power of two >= the number of distinct levels
+ *             255 q in sample b over all channels; noise = poisson(q * vals_b) / vals_b - q; the grey field of a sample likewise from
+ *             g = clamp(rint(255 (0.2989 R + 0.587 G + 0.114 B)), 0, 255) / 255 and its own vals, one count per pixel shared by
+ *             the three channels; noise = (noise * (1 - g_b) + noise_grey * g_b) * scale_b
+ *   out = epilogue(img + noise), or epilogue(noise) with OSS_NOISE_ONLY (generate_*; img may then be NULL for Gaussian)
+ *   sigma_b / scale_b, g_b   sigma[b] / scale[b] and gray[b] from (batch,) fp32 arrays in DEVICE memory; a NULL array stands for the
+ *             scalar sigma_lo / scale_lo resp. gray_scalar.  OSS_NOISE_DRAW_PARAMS (random_*): both are drawn by the kernel,
+ *             sigma_b = u (hi - lo) + lo and g_b = (u' < gray_scalar) with u, u' uniform in [0, 1) with 24 bits; the arrays are not read.
+ *             The grey term is always evaluated and mixed with its weight (the package skips it after a host read when all g_b
+ *             are 0: the same value).
+ *   epilogue  OSS_NOISE_CLIP: clamp to [0, 1]; OSS_NOISE_ROUNDS: rint(x * 255) / 255; both: clamp(rint(x * 255), 0, 255) / 255;
+ *             OSS_NOISE_QUANTISE: then clamp(rint(x * 255), 0, 255) / 255 with the bits of OSS_FILTER_QUANTISE (/ 255 as torch
+ *             evaluates it on the device)
+ *   params    may be NULL; else fp32, (2, batch) for Gaussian: sigma_b, g_b as used; (4, batch) for Poisson: scale_b, g_b, vals_b of
+ *             the colour levels, vals_b of the grey levels
+ *   OSS_NOISE_RAW   the samplers alone.  Gaussian: out = n_c (img unused, may be NULL).  Poisson: img holds lambda (clamped to
+ *             256) per element, out receives the count drawn with that element's colour draws; any channels, no scratch.
+ *             gray_scalar > 0 selects the grey draws instead: n_g[y, x] of every element, resp. the counts with the grey tag and
+ *             element = flat index (the grey counts of a (batch, 3, h, w) call when img is its (batch, 1, h, w) lambda field).
+ * Random stream: every word is a word of Philox4x32-10 with key (seed lo, seed hi) and counter (element lo, element hi [8 bits] | call
+ * hi << 8, tag << 24 | draw, call lo); tags 0x63 colour, 0x67 grey, 0x70 parameters (element = b, words 0 and 1).  Gaussian: element
+ * = flat index / 4 (colour) or (y w + x) / 4 (grey, no sample index), draw 0, the normals of the 4 elements by Box-Muller on the word
+ * pairs (0, 1) and (2, 3): u1 = (word + 1/2) 2^-32, r = sqrt(-2 ln u1) (ln u1 as log1p(-(~word + 1/2) 2^-32) for word >= 2^31),
+ * theta = 2 pi word' 2^-32, (r cos theta, r sin theta).
+ * Poisson: element = flat index (colour) or b h w + pixel (grey); lambda < OSS_NOISE_POISSON_SWITCH: inversion by sequential search in
+ * fp64 from u = (word 0 of draw 0 + 1/2) 2^-32, at most OSS_NOISE_INVERSION_MAX steps; else PTRS (Hoermann 1993), round i with
+ * the words 2 (i & 1), 2 (i & 1) + 1 of draw i / 2 as ((word >> 9) + 1/2) 2^-23, at most OSS_NOISE_PTRS_MAX_ROUNDS rounds (then
+ * floor(lambda): probability below 1e-13).
+ *   state     two int64 in DEVICE memory: seed, call.  The kernels read both; a one-thread launch after the sampling launch stores
+ *             call + 1, so the next call -- or the next replay of a captured one -- draws other fields.  One call consumes one value.
+ *   scratch   Poisson without OSS_NOISE_RAW: oss_noise_scratch_words(batch) = 16 batch uint32 words, zeroed by the entry point on
+ *             the stream: per sample the 256-bit set of colour levels and the 256-bit set of grey levels, filled by a census launch.
+ * Launches: Gaussian sampling + advance; Poisson memset + census + sampling + advance.  Nothing is allocated or read back.
+ * oss_noise_workgroups(kind: 0 Gaussian, 1 Poisson, ...) is a pure host call and the support query: the sampling launch's
+ * workgroups, 0 when refused -- an unknown kind or flag, a dimension < 1 or above 2^24, 2^40 or more elements, more than 2^31 - 1
+ * workgroups, and for Poisson without OSS_NOISE_RAW channels != 3 or batch > 65535.  The entry points return OSS_ERR_SHAPE for the
+ * same and for out == img, OSS_ERR_NULL for a missing out, state, scratch (where needed) or img (where needed), without a launch.
+ * The *_host twins evaluate the same per-element text on the CPU with all pointers in HOST memory and (key, counter) = (seed, call)
+ * as plain numbers; they advance nothing.  oss_noise_normals_host applies the normal transform alone to `blocks` groups of four GIVEN
+ * words (host memory) -> four fp32 normals each, for the words no seed is known to produce (all-zero, all-one bits). */
+#define OSS_NOISE_DRAW_PARAMS 1
+#define OSS_NOISE_CLIP 2
+#define OSS_NOISE_ROUNDS 4
+#define OSS_NOISE_QUANTISE 8
+#define OSS_NOISE_RAW 16
+#define OSS_NOISE_ONLY 32
+#define OSS_NOISE_POISSON_SWITCH 10
+#define OSS_NOISE_INVERSION_MAX 64
+#define OSS_NOISE_PTRS_MAX_ROUNDS 16
+size_t oss_noise_workgroups(int kind, int64_t batch, int64_t channels, int64_t h, int64_t w, int flags);
+size_t oss_noise_scratch_words(int64_t batch);
+int oss_noise_gaussian(const float *img, float *out, int64_t *state, const float *sigma, const float *gray, float sigma_lo,
+                       float sigma_hi, float gray_scalar, float *params, int64_t batch, int64_t channels, int64_t h, int64_t w,
+                       int flags, oss_stream_t stream);
+int oss_noise_poisson(const float *img, float *out, int64_t *state, const float *scale, const float *gray, float scale_lo,
+                      float scale_hi, float gray_scalar, float *params, uint32_t *scratch, int64_t batch, int64_t channels, int64_t h,
+                      int64_t w, int flags, oss_stream_t stream);
+int oss_noise_normals_host(const uint32_t *words, float *out, int64_t blocks);
+int oss_noise_gaussian_host(const float *img, float *out, int64_t key, int64_t counter, const float *sigma, const float *gray,
+                            float sigma_lo, float sigma_hi, float gray_scalar, float *params, int64_t batch, int64_t channels,
+                            int64_t h, int64_t w, int flags);
+int oss_noise_poisson_host(const float *img, float *out, int64_t key, int64_t counter, const float *scale, const float *gray,
+                           float scale_lo, float scale_hi, float gray_scalar, float *params, uint32_t *scratch, int64_t batch,
+                           int64_t channels, int64_t h, int64_t w, int flags);
+
 /* The reference's pixel losses with their gradients on the device (oss_pixel_loss.hip): L1Loss, MSELoss, PSNRLoss (with toY) and
  * CharbonnierLoss of Deraining/basicsr/models/losses/losses.py:26-122 with the weighting and reduction of weight_reduce_loss
  * (losses/loss_util.py:25-54).  lw = loss_weight, d = pred - target, n = batch * channels * plane:
@@ -997,12 +1067,13 @@ int oss_f32_matmul_modes(void);
  * every change of a struct or of an entry point's argument list (9: the pre-packed weight images of the 1x1 convolutions,
  * oss_conv1x1_pack_* and the *_packed entry points; 10: oss_chan_params lost zt and dts, the channel kernels evaluate the
  * projections from the pooled vector; 11: the added entry point oss_proj_set_one_launch; 12: the added
- * entry points oss_jpeg_workgroups and oss_jpeg_roundtrip); oss_abi_struct_bytes(which) is the library's own sizeof
+ * entry points oss_jpeg_workgroups and oss_jpeg_roundtrip; 13: the added entry points oss_noise_workgroups,
+ * oss_noise_scratch_words, oss_noise_gaussian, oss_noise_poisson, their *_host twins and oss_noise_normals_host); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 12
+#define OSS_ABI_VERSION 13
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

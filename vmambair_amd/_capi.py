@@ -23,6 +23,7 @@ NIQE_BLOCK, NIQE_FEATURES, NIQE_GRID = _K["OSS_NIQE_BLOCK"], _K["OSS_NIQE_FEATUR
 LOSS = {k[len("OSS_LOSS_"):]: v for k, v in _K.items() if k.startswith("OSS_LOSS_")}   # kinds and flags of oss_pixel_loss_fwd / _bwd
 FILTER = {k[len("OSS_FILTER"):].lstrip("_"): v for k, v in _K.items() if k.startswith("OSS_FILTER")}   # epilogues and tap limits of oss_filter2d / _sep
 JPEG = {k[len("OSS_JPEG_"):]: v for k, v in _K.items() if k.startswith("OSS_JPEG_")}   # flags of oss_jpeg_roundtrip
+NOISE = {k[len("OSS_NOISE_"):]: v for k, v in _K.items() if k.startswith("OSS_NOISE_")}   # flags and sampler limits of oss_noise_gaussian / _poisson
 PAIRS_HFLIP, PAIRS_ROT = _K["OSS_PAIRS_HFLIP"], _K["OSS_PAIRS_ROT"]   # flags of oss_pairs_draw
 FEATURE_FUSED_DT, FEATURE_LANE_STATES = _K["OSS_FEATURE_FUSED_DT"], _K["OSS_FEATURE_LANE_STATES"]   # oss_scan_features()
 ADAM_CHUNK = _K["OSS_ADAM_CHUNK"]

@@ -54,23 +54,11 @@
 //
 // hipcc -Rpass-analysis=kernel-resource-usage, gfx950: see DESIGN.md 4.4d.  Timings: profiles/pairs_kernel_timing.txt.
 #include "oss_host.h"
+#include "oss_philox.h"   // Philox4x32-10, host and device from one text
 
 #include <type_traits>
 
 namespace oss {
-
-// ---- Philox4x32-10 (Salmon et al., SC'11; the constants of Random123), host and device from one text ---------------------------
-struct Philox4 { uint32_t v[4]; };
-
-__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
 
 constexpr uint32_t kTagPerm = 0x7065726du, kTagCrop = 0x63726f70u;   // "perm", "crop": word 3 / word 2 of the two counter forms
 constexpr uint32_t kTagWind = 0x77696e64u;                           // "wind": word 2 of the per-call window block

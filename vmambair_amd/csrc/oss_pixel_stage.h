@@ -12,12 +12,12 @@ constexpr float kInv255 = (float)(1.0 / 255.0);
 
 // torch's clamp gives +0 for -0 and for everything below 0; the "+ 0.0f" makes that independent of the max instruction's operand
 // order.  A NaN stays a NaN.
-__device__ __forceinline__ float clamp_unit(float v) {
+__host__ __device__ __forceinline__ float clamp_unit(float v) {
     return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f) + 0.0f;
 }
 
 // clamp(round(v * 255), 0, 255) / 255 with round-half-even
-__device__ __forceinline__ float quantise_255(float v) {
+__host__ __device__ __forceinline__ float quantise_255(float v) {
 #pragma clang fp contract(off)
     const float r = rintf(v * 255.0f);
     return (r != r ? r : fminf(fmaxf(r, 0.0f), 255.0f) + 0.0f) * kInv255;

@@ -5,6 +5,7 @@ every training step (RealSR/VmambaIR/models/MambaRealSR_model.py:146-263):
   ``USMSharp(radius=50, sigma=0)``  unsharp masking of the ground truth with a 51 x 51 Gaussian (:154-155, :262)
   ``gaussian_kernel1d(k, sigma)``   the Gaussian vector ``USMSharp`` is built from
   ``DiffJPEG(differentiable)``      JPEG compression and decompression with a quality per sample (:86, :189-191, :234-241)
+  ``random_add_gaussian_noise_pt``, ``random_add_poisson_noise_pt`` and their six siblings: the two noise branches (:177-187, :209-219)
   ``TrainingPairPool(queue_size)``  the training pair pool ``_dequeue_and_enqueue`` (:109-144)
 
 The reference imports ``filter2D``, ``USMSharp`` and ``DiffJPEG`` from the pip ``basicsr`` package (``basicsr.utils``,
@@ -22,8 +23,14 @@ backward exists: the device paths run under ``torch.no_grad`` and return tensors
 CPU tensors, non-fp32 input, k above the kernels' limits and, in ``filter2D``, a large (1, k, k) kernel, which need not be rank 1 -- as
 ``losses.py`` and ``metrics.py`` do for CPU inputs.  ``DiffJPEG`` on a contiguous fp32 device tensor is one launch of
 ``csrc/oss_jpeg.hip`` (``torch.ops.vmambair.jpeg_roundtrip``) per call, with the quality of every sample read on the device; its
-restatement ``restate_diffjpeg`` follows the package operation by operation.  What is left of ``feed_data`` -- ``F.interpolate`` and
-the two noise functions -- is plain torch.
+restatement ``restate_diffjpeg`` follows the package operation by operation.  The two noise steps (:177-187, :209-219) -- the eight
+``*_gaussian_noise_pt`` / ``*_poisson_noise_pt`` functions of ``basicsr.data.degradations``, here with the package's names,
+positional signatures and defaults -- run on ``csrc/oss_noise.hip`` (``torch.ops.vmambair.noise_gaussian`` / ``noise_poisson``): one
+sampling launch for the Gaussian noise, a level census and a sampling launch for the Poisson noise, both drawing from a
+``NoiseStream`` -- a Philox4x32-10 key and a call counter in device memory -- without a host read, so that a whole degradation
+stage (``filter2D`` -> ``F.interpolate`` -> noise -> ``DiffJPEG``) can be captured into a graph and draws a new field at every replay;
+their restatements ``restate_*_noise_pt`` follow the package operation by operation, host reads and ``unique`` loop included.  What
+is left of ``feed_data`` is ``F.interpolate``, a vendor operator that is one launch without a host read.
 """
 from __future__ import annotations
 
@@ -304,6 +311,342 @@ class DiffJPEG(nn.Module):
         if quantise:
             out = restate_quantise(out)
         return (out, coef) if return_coefficients else out
+
+
+# ---------------------------------------------------------------------------------------------
+# the two noise steps (basicsr.data.degradations, the *_pt functions)
+# ---------------------------------------------------------------------------------------------
+def _is_number(v) -> bool:
+    return isinstance(v, (float, int))
+
+
+def _rgb_to_grayscale(img: torch.Tensor) -> torch.Tensor:
+    """torchvision.transforms.functional.rgb_to_grayscale(img, num_output_channels=1), which the package calls"""
+    if img.shape[-3] not in (1, 3):
+        raise TypeError(f"Input image tensor permitted channel values are [1, 3], but found {img.shape[-3]}")
+    if img.shape[-3] == 1:
+        return img.clone()
+    r, g, b = img.unbind(dim=-3)
+    return (0.2989 * r + 0.587 * g + 0.114 * b).to(img.dtype).unsqueeze(dim=-3)
+
+
+def _poisson_vals(levels: torch.Tensor) -> list:
+    """the package's ``vals`` of a quantised (B, C, h, w) image: per sample 2 ** ceil(log2(number of distinct values)) -- a sort and a
+    read-back per sample"""
+    return [2 ** math.ceil(math.log2(len(torch.unique(levels[i, :, :, :])))) for i in range(levels.size(0))]
+
+
+def _restate_finish(out: torch.Tensor, clip: bool, rounds: bool) -> torch.Tensor:
+    if clip and rounds:
+        return torch.clamp((out * 255.0).round(), 0, 255) / 255.
+    if clip:
+        return torch.clamp(out, 0, 1)
+    if rounds:
+        return (out * 255.0).round() / 255.
+    return out
+
+
+def restate_generate_gaussian_noise_pt(img: torch.Tensor, sigma=10, gray_noise=0) -> torch.Tensor:
+    """basicsr.data.degradations.generate_gaussian_noise_pt, operation by operation, from torch's default generator of img's
+    device: the host read ``torch.sum(gray_noise) > 0`` and the ONE (h, w) grey field shared by the batch included (with a number
+    ``sigma`` that field cannot be viewed as (b, 1, h, w) for b > 1 and the call raises, as the package's does)"""
+    b, _, h, w = img.size()
+    if not _is_number(sigma):
+        sigma = sigma.view(img.size(0), 1, 1, 1)
+    if _is_number(gray_noise):
+        cal_gray_noise = gray_noise > 0
+    else:
+        gray_noise = gray_noise.view(b, 1, 1, 1)
+        cal_gray_noise = torch.sum(gray_noise) > 0
+    if cal_gray_noise:
+        noise_gray = torch.randn(*img.size()[2:4], dtype=img.dtype, device=img.device) * sigma / 255.
+        noise_gray = noise_gray.view(b, 1, h, w)
+    noise = torch.randn(*img.size(), dtype=img.dtype, device=img.device) * sigma / 255.
+    if cal_gray_noise:
+        noise = noise * (1 - gray_noise) + noise_gray * gray_noise
+    return noise
+
+
+def restate_generate_poisson_noise_pt(img: torch.Tensor, scale=1.0, gray_noise=0) -> torch.Tensor:
+    """basicsr.data.degradations.generate_poisson_noise_pt, operation by operation: ``torch.poisson`` from the default generator,
+    the ``unique`` loop over the samples (twice) and the host read of ``gray_noise`` included.  Grey noise needs 1 or 3 channels
+    (``rgb_to_grayscale`` raises ``TypeError`` otherwise) and is expanded to 3."""
+    b, _, h, w = img.size()
+    if _is_number(gray_noise):
+        cal_gray_noise = gray_noise > 0
+    else:
+        gray_noise = gray_noise.view(b, 1, 1, 1)
+        cal_gray_noise = torch.sum(gray_noise) > 0
+    if cal_gray_noise:
+        img_gray = _rgb_to_grayscale(img)
+        img_gray = torch.clamp((img_gray * 255.0).round(), 0, 255) / 255.
+        vals = img_gray.new_tensor(_poisson_vals(img_gray)).view(b, 1, 1, 1)
+        out = torch.poisson(img_gray * vals) / vals
+        noise_gray = out - img_gray
+        noise_gray = noise_gray.expand(b, 3, h, w)
+    img = torch.clamp((img * 255.0).round(), 0, 255) / 255.
+    vals = img.new_tensor(_poisson_vals(img)).view(b, 1, 1, 1)
+    out = torch.poisson(img * vals) / vals
+    noise = out - img
+    if cal_gray_noise:
+        noise = noise * (1 - gray_noise) + noise_gray * gray_noise
+    if not _is_number(scale):
+        scale = scale.view(b, 1, 1, 1)
+    return noise * scale
+
+
+def _restate_random_params(img: torch.Tensor, value_range, gray_prob):
+    """the draws of random_generate_*_noise_pt, in the package's order"""
+    amount = torch.rand(img.size(0), dtype=img.dtype, device=img.device) * (value_range[1] - value_range[0]) + value_range[0]
+    gray_noise = torch.rand(img.size(0), dtype=img.dtype, device=img.device)
+    return amount, (gray_noise < gray_prob).float()
+
+
+def restate_random_generate_gaussian_noise_pt(img: torch.Tensor, sigma_range=(0, 10), gray_prob=0) -> torch.Tensor:
+    """basicsr.data.degradations.random_generate_gaussian_noise_pt"""
+    sigma, gray_noise = _restate_random_params(img, sigma_range, gray_prob)
+    return restate_generate_gaussian_noise_pt(img, sigma, gray_noise)
+
+
+def restate_random_generate_poisson_noise_pt(img: torch.Tensor, scale_range=(0, 1.0), gray_prob=0) -> torch.Tensor:
+    """basicsr.data.degradations.random_generate_poisson_noise_pt"""
+    scale, gray_noise = _restate_random_params(img, scale_range, gray_prob)
+    return restate_generate_poisson_noise_pt(img, scale, gray_noise)
+
+
+def restate_add_gaussian_noise_pt(img, sigma=10, gray_noise=0, clip=True, rounds=False):
+    """basicsr.data.degradations.add_gaussian_noise_pt"""
+    return _restate_finish(img + restate_generate_gaussian_noise_pt(img, sigma, gray_noise), clip, rounds)
+
+
+def restate_add_poisson_noise_pt(img, scale=1.0, clip=True, rounds=False, gray_noise=0):
+    """basicsr.data.degradations.add_poisson_noise_pt (``clip`` and ``rounds`` come before ``gray_noise`` in this one)"""
+    return _restate_finish(img + restate_generate_poisson_noise_pt(img, scale, gray_noise), clip, rounds)
+
+
+def restate_random_add_gaussian_noise_pt(img, sigma_range=(0, 10), gray_prob=0, clip=True, rounds=False):
+    """basicsr.data.degradations.random_add_gaussian_noise_pt"""
+    return _restate_finish(img + restate_random_generate_gaussian_noise_pt(img, sigma_range, gray_prob), clip, rounds)
+
+
+def restate_random_add_poisson_noise_pt(img, scale_range=(0, 1.0), gray_prob=0, clip=True, rounds=False):
+    """basicsr.data.degradations.random_add_poisson_noise_pt"""
+    return _restate_finish(img + restate_random_generate_poisson_noise_pt(img, scale_range, gray_prob), clip, rounds)
+
+
+def _indexed_device(device) -> torch.device:
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        return torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+class NoiseStream:
+    """The random stream of the device noise functions: a (2,) int64 tensor in device memory, ``seed`` (the Philox key) and ``call``
+    (the number of noise calls made so far).  The kernels read both on the device and a one-thread launch after the sampling
+    launch stores ``call + 1``: nothing is read back, and a call captured into a graph draws a new field at every replay -- the
+    fields N eager calls from the same state draw.  The tensor is created at the first use on a device (or at construction with
+    ``device=``), which must happen outside a capture, and a stream serves one device.  ``state_dict()`` reads the two numbers back
+    (the only read-back here), ``load_state_dict()`` writes them into the same tensor, so a captured graph follows a resumed run."""
+
+    def __init__(self, seed: int, device=None):
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.seed = seed - (1 << 64) if seed >= (1 << 63) else seed     # as the int64 the device holds
+        self._state: Optional[torch.Tensor] = None
+        if device is not None:
+            self.state(torch.device(device))
+
+    def state(self, device) -> torch.Tensor:
+        device = _indexed_device(device)
+        if self._state is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("NoiseStream: the first use on a device creates the state tensor, which cannot happen inside a "
+                                   "graph capture; construct the stream with device=, or call a noise function once before capturing")
+            self._state = torch.tensor([self.seed, 0], dtype=torch.int64, device=device)
+        if self._state.device != device:
+            raise RuntimeError(f"NoiseStream: the stream lives on {self._state.device}, the image on {device}")
+        return self._state
+
+    def clone(self) -> "NoiseStream":
+        """a stream that continues from this one's present state, independently"""
+        other = NoiseStream(self.seed)
+        if self._state is not None:
+            other._state = self._state.clone()
+        return other
+
+    def state_dict(self) -> dict:
+        seed, calls = (self.seed, 0) if self._state is None else self._state.tolist()
+        return {"seed": seed, "calls": calls}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.seed = int(state["seed"])
+        if self._state is None:
+            if int(state["calls"]):
+                raise RuntimeError("NoiseStream: bind the stream to a device (device=) before loading a state that has made calls")
+            return
+        self._state.copy_(torch.tensor([self.seed, int(state["calls"])], dtype=torch.int64))
+
+
+_DEFAULT_NOISE_STREAMS: dict = {}
+
+
+def default_noise_stream(device) -> NoiseStream:
+    """the module's stream of ``device``, seeded from ``torch.initial_seed()`` at its first use"""
+    device = _indexed_device(device)
+    if device not in _DEFAULT_NOISE_STREAMS:
+        _DEFAULT_NOISE_STREAMS[device] = NoiseStream(torch.initial_seed(), device)
+    return _DEFAULT_NOISE_STREAMS[device]
+
+
+def _noise_on_device(kind: int, img: torch.Tensor, amount, gray_noise) -> bool:
+    """a contiguous fp32 device image the kernels take, with ``amount`` / ``gray_noise`` numbers or (B,) tensors"""
+    if not (torch.is_tensor(img) and img.is_cuda and img.is_contiguous() and _ops.noise_ok(img, kind)):
+        return False
+    return all(_is_number(v) or (torch.is_tensor(v) and v.numel() == img.size(0)) for v in (amount, gray_noise))
+
+
+def _noise_device(kind: int, img, stream, amount, gray_noise, flags: int, want_params: bool):
+    n = _ops.noise
+    state = (stream if stream is not None else default_noise_stream(img.device)).state(img.device)
+    if flags & n.DRAW_PARAMS:
+        (lo, hi), gray_scalar, amount_t, gray_t = amount, gray_noise, None, None
+    else:
+        as_vector = lambda v: None if _is_number(v) else v.detach().reshape(-1).to(device=img.device, dtype=torch.float32).contiguous()
+        amount_t, gray_t = as_vector(amount), as_vector(gray_noise)
+        lo = hi = float(amount) if amount_t is None else 0.0
+        gray_scalar = float(gray_noise) if gray_t is None else 0.0
+    with torch.no_grad():
+        op = _ops.noise_gaussian if kind == n.GAUSSIAN else _ops.noise_poisson
+        return op(img, state, amount_t, gray_t, float(lo), float(hi), float(gray_scalar), flags, want_params)
+
+
+def _noise_flags(clip: bool, rounds: bool, quantise: bool) -> int:
+    n = _ops.noise
+    return (n.CLIP if clip else 0) | (n.ROUNDS if rounds else 0) | (n.QUANTISE if quantise else 0)
+
+
+_NOISE_DOC = """
+
+    A contiguous fp32 device tensor runs on ``csrc/oss_noise.hip`` (``torch.ops.vmambair.noise_{kind}``) under ``no_grad``, drawing
+    from ``stream`` (a ``NoiseStream``; default: the module's stream of the device, seeded from ``torch.initial_seed()`` at its
+    first use).  CPU tensors, other dtypes, non-contiguous views{extra} and shapes the kernels refuse take ``restate_{name}``, the
+    package's operations in plain torch from torch's generator.  Deviations of the device path from the package: nothing is read
+    back to the host -- the grey term is always evaluated and mixed with weight 0 or 1, which is algebraically the package's
+    result, and the level census of the Poisson noise stays on the device; the Gaussian grey field is ONE (h, w) field shared by
+    all samples, as the package has it, and a number ``sigma`` with grey noise works for any batch (the package can only view it
+    for b = 1); the random numbers are Philox4x32-10 words (counter layout: include/vmambair_oss.h), not torch's, so a seed
+    reproduces the distribution of the package's samples, not the samples."""
+
+
+def _noise_doc(kind: str, name: str, extra: str = ""):
+    def wrap(f):
+        f.__doc__ += _NOISE_DOC.format(kind=kind, name=name, extra=extra)
+        return f
+    return wrap
+
+
+@_noise_doc("gaussian", "generate_gaussian_noise_pt")
+def generate_gaussian_noise_pt(img, sigma=10, gray_noise=0, *, stream: Optional[NoiseStream] = None):
+    """basicsr.data.degradations.generate_gaussian_noise_pt: the noise ``randn * sigma / 255`` for ``img`` (B, C, h, w), colour noise
+    mixed with grey noise by the weights ``gray_noise``; ``sigma`` and ``gray_noise`` are numbers or (B,) tensors."""
+    if _noise_on_device(0, img, sigma, gray_noise):
+        return _noise_device(0, img, stream, sigma, gray_noise, _ops.noise.ONLY, False)[0]
+    return restate_generate_gaussian_noise_pt(img, sigma, gray_noise)
+
+
+@_noise_doc("gaussian", "add_gaussian_noise_pt")
+def add_gaussian_noise_pt(img, sigma=10, gray_noise=0, clip=True, rounds=False, *, stream: Optional[NoiseStream] = None,
+                          quantise: bool = False):
+    """basicsr.data.degradations.add_gaussian_noise_pt: ``img + generate_gaussian_noise_pt(img, sigma, gray_noise)``, then ``clip``
+    to [0, 1] and / or ``rounds`` to multiples of 1 / 255.  ``quantise`` applies ``clamp((x * 255).round(), 0, 255) / 255`` last
+    (MambaRealSR_model.py:248), on the device as a stage of the same launch."""
+    if _noise_on_device(0, img, sigma, gray_noise):
+        return _noise_device(0, img, stream, sigma, gray_noise, _noise_flags(clip, rounds, quantise), False)[0]
+    out = restate_add_gaussian_noise_pt(img, sigma, gray_noise, clip, rounds)
+    return restate_quantise(out) if quantise else out
+
+
+@_noise_doc("gaussian", "random_generate_gaussian_noise_pt")
+def random_generate_gaussian_noise_pt(img, sigma_range=(0, 10), gray_prob=0, *, stream: Optional[NoiseStream] = None,
+                                      return_params: bool = False):
+    """basicsr.data.degradations.random_generate_gaussian_noise_pt: ``sigma`` ~ U[sigma_range) and ``gray_noise`` = 1 with
+    probability ``gray_prob`` per sample, then ``generate_gaussian_noise_pt``.  ``return_params``: -> (noise, sigma, gray_noise)
+    with the (B,) values drawn (on the device: by the kernel)."""
+    if _noise_on_device(0, img, 0, 0):
+        n = _ops.noise
+        out, params = _noise_device(0, img, stream, sigma_range, gray_prob, n.ONLY | n.DRAW_PARAMS, return_params)
+        return (out, params[0], params[1]) if return_params else out
+    sigma, gray_noise = _restate_random_params(img, sigma_range, gray_prob)
+    out = restate_generate_gaussian_noise_pt(img, sigma, gray_noise)
+    return (out, sigma, gray_noise) if return_params else out
+
+
+@_noise_doc("gaussian", "random_add_gaussian_noise_pt")
+def random_add_gaussian_noise_pt(img, sigma_range=(0, 10), gray_prob=0, clip=True, rounds=False, *,
+                                 stream: Optional[NoiseStream] = None, return_params: bool = False, quantise: bool = False):
+    """basicsr.data.degradations.random_add_gaussian_noise_pt, the first noise branch of ``feed_data`` (MambaRealSR_model.py:177-180,
+    :209-212): ``img + random_generate_gaussian_noise_pt(img, sigma_range, gray_prob)``, then ``clip`` / ``rounds``.
+    ``return_params``: -> (out, sigma, gray_noise); ``quantise``: ``clamp((x * 255).round(), 0, 255) / 255`` last."""
+    if _noise_on_device(0, img, 0, 0):
+        flags = _noise_flags(clip, rounds, quantise) | _ops.noise.DRAW_PARAMS
+        out, params = _noise_device(0, img, stream, sigma_range, gray_prob, flags, return_params)
+        return (out, params[0], params[1]) if return_params else out
+    sigma, gray_noise = _restate_random_params(img, sigma_range, gray_prob)
+    out = _restate_finish(img + restate_generate_gaussian_noise_pt(img, sigma, gray_noise), clip, rounds)
+    out = restate_quantise(out) if quantise else out
+    return (out, sigma, gray_noise) if return_params else out
+
+
+@_noise_doc("poisson", "generate_poisson_noise_pt", ", images without exactly 3 channels")
+def generate_poisson_noise_pt(img, scale=1.0, gray_noise=0, *, stream: Optional[NoiseStream] = None):
+    """basicsr.data.degradations.generate_poisson_noise_pt: with ``q = clamp((img * 255).round(), 0, 255) / 255`` and ``vals`` = the
+    next power of two >= the number of distinct values of ``q`` in a sample, ``(poisson(q * vals) / vals - q) * scale``; the grey
+    noise likewise from the sample's grey image, one count per pixel for the three channels, mixed in by ``gray_noise``."""
+    if _noise_on_device(1, img, scale, gray_noise):
+        return _noise_device(1, img, stream, scale, gray_noise, _ops.noise.ONLY, False)[0]
+    return restate_generate_poisson_noise_pt(img, scale, gray_noise)
+
+
+@_noise_doc("poisson", "add_poisson_noise_pt", ", images without exactly 3 channels")
+def add_poisson_noise_pt(img, scale=1.0, clip=True, rounds=False, gray_noise=0, *, stream: Optional[NoiseStream] = None,
+                         quantise: bool = False):
+    """basicsr.data.degradations.add_poisson_noise_pt (the package puts ``clip`` and ``rounds`` before ``gray_noise`` here):
+    ``img + generate_poisson_noise_pt(img, scale, gray_noise)``, then ``clip`` / ``rounds``; ``quantise`` as in
+    ``add_gaussian_noise_pt``."""
+    if _noise_on_device(1, img, scale, gray_noise):
+        return _noise_device(1, img, stream, scale, gray_noise, _noise_flags(clip, rounds, quantise), False)[0]
+    out = restate_add_poisson_noise_pt(img, scale, clip, rounds, gray_noise)
+    return restate_quantise(out) if quantise else out
+
+
+@_noise_doc("poisson", "random_generate_poisson_noise_pt", ", images without exactly 3 channels")
+def random_generate_poisson_noise_pt(img, scale_range=(0, 1.0), gray_prob=0, *, stream: Optional[NoiseStream] = None,
+                                     return_params: bool = False):
+    """basicsr.data.degradations.random_generate_poisson_noise_pt: ``scale`` ~ U[scale_range) and ``gray_noise`` = 1 with
+    probability ``gray_prob`` per sample, then ``generate_poisson_noise_pt``.  ``return_params``: -> (noise, scale, gray_noise)."""
+    if _noise_on_device(1, img, 0, 0):
+        n = _ops.noise
+        out, params = _noise_device(1, img, stream, scale_range, gray_prob, n.ONLY | n.DRAW_PARAMS, return_params)
+        return (out, params[0], params[1]) if return_params else out
+    scale, gray_noise = _restate_random_params(img, scale_range, gray_prob)
+    out = restate_generate_poisson_noise_pt(img, scale, gray_noise)
+    return (out, scale, gray_noise) if return_params else out
+
+
+@_noise_doc("poisson", "random_add_poisson_noise_pt", ", images without exactly 3 channels")
+def random_add_poisson_noise_pt(img, scale_range=(0, 1.0), gray_prob=0, clip=True, rounds=False, *,
+                                stream: Optional[NoiseStream] = None, return_params: bool = False, quantise: bool = False):
+    """basicsr.data.degradations.random_add_poisson_noise_pt, the second noise branch of ``feed_data`` (MambaRealSR_model.py:181-187,
+    :213-219): ``img + random_generate_poisson_noise_pt(img, scale_range, gray_prob)``, then ``clip`` / ``rounds``.
+    ``return_params``: -> (out, scale, gray_noise); ``quantise``: ``clamp((x * 255).round(), 0, 255) / 255`` last."""
+    if _noise_on_device(1, img, 0, 0):
+        flags = _noise_flags(clip, rounds, quantise) | _ops.noise.DRAW_PARAMS
+        out, params = _noise_device(1, img, stream, scale_range, gray_prob, flags, return_params)
+        return (out, params[0], params[1]) if return_params else out
+    scale, gray_noise = _restate_random_params(img, scale_range, gray_prob)
+    out = _restate_finish(img + restate_generate_poisson_noise_pt(img, scale, gray_noise), clip, rounds)
+    out = restate_quantise(out) if quantise else out
+    return (out, scale, gray_noise) if return_params else out
 
 
 class TrainingPairPool:

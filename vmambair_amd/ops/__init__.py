@@ -13,6 +13,7 @@ One module per operator family (round 1 had a single 1 000-line ``ops.py``):
                 features of the no-reference NIQE per 96 x 96 block of a batch of images
   ``degrade``   filter2D (a k x k kernel per sample, reflect padded), USM sharpening and the JPEG round trip (DiffJPEG, one launch) of the
                 RealSR degradation pipeline, fp32
+  ``noise``     the Gaussian and Poisson noise steps of the same pipeline, drawn from a counter-based stream in device memory
   ``losses``    the pixel losses (L1, MSE, Charbonnier, PSNR) with their gradient w.r.t. the prediction: fp64 sums in a fixed order
   ``pairs``     training batches cut from a device-resident pool of image pairs: counter-based draw + one crop / flip / convert launch
   ``_common``   dtype table, checks, deferred finishing, weight-gradient side stream
@@ -23,7 +24,7 @@ No CPU implementation exists: CPU tensors are rejected exactly as the reference 
 cus/selective_scan.cpp:174).
 """
 from .. import _capi  # noqa: F401
-from . import _common, channel, conv3x3, core, degrade, dwconv, ffn, layernorm, losses, metrics, pairs, pointwise, scan  # noqa: F401
+from . import _common, channel, conv3x3, core, degrade, dwconv, ffn, layernorm, losses, metrics, noise, pairs, pointwise, scan  # noqa: F401
 from ._common import (WGRAD_STATS, WgradTable, flush_wgrads, pending_wgrad_table_bytes, pending_wgrads, _keep_operands,  # noqa: F401
                       FinishTable, _DT, _LIB, _check, _f32c, _fork_for_wgrad, _keep, _keep_views, _planes, _ptr,  # noqa: F401
                       deferred_finishes, flush_finishes, orphaned_deferred_outputs, pending_finish_chunks, scan_chunk,
@@ -41,6 +42,7 @@ from .conv3x3 import conv3x3 as conv3x3_layer  # noqa: F401
 from .ffn import GeluGateFn, effn_fwd, effn_fwd_ok, effn_round_weights, gelu_gate, gelu_gate_bwd, gelu_gate_fwd  # noqa: F401
 from .layernorm import _CODE_DT, _DT_CODE, LayerNormNCHWFn, layer_norm_nchw, ln_nchw_bwd, ln_nchw_fwd  # noqa: F401
 from .degrade import filter2d, filter2d_ok, filter_sep, filter_sep_ok, jpeg_ok, jpeg_roundtrip, usm_sharp  # noqa: F401
+from .noise import noise_gaussian, noise_ok, noise_poisson  # noqa: F401
 from .losses import pixel_loss_bwd, pixel_loss_fwd, pixel_loss_ok  # noqa: F401
 from .metrics import image_metrics, image_metrics_ok, niqe_features, niqe_features_ok  # noqa: F401
 from .pairs import pairs_draw, pairs_draw_window, pairs_gather, pairs_gather_padded, pairs_ok  # noqa: F401
