@@ -441,6 +441,23 @@ int oss_conv1x1_dgrad_ln_bwd(oss_dtype io, const void *dy, const float *weight, 
 /* A-B switches of the dispatch inside oss_conv1x1_fwd / _dgrad: on = 0 never takes the workgroup-level kernel (the
  * library starts with on = 1); pixels = 64 | 128 forces its tile width, 0 = by grid size (the start value) */
 void oss_conv1x1_set_wg(int on, int pixels);
+/* What oss_conv1x1_fwd_packed (input_gradient = 0) / oss_conv1x1_dgrad_packed (1) would launch for these arguments and the
+ * switches above, without launching it: the plan of csrc/oss_conv1x1_plan.h that the launchers themselves run.  Pure host
+ * arithmetic on the shape, the strides, the low 4 address bits of x, weight, image, residual and y and on which of image / bias /
+ * residual are NULL; nothing is dereferenced.  x / y are dy / dx of the input gradient, which ignores bias and residual; image ==
+ * NULL or fp32 io: the unpacked entry point.  Returns what the entry point would return before its launch (OSS_ERR_*). */
+typedef struct {
+    int family;        /* kernel: 0 wg (workgroup-level), 1 pair, 2 pairw, 3 pairk, 4 reuse, 5 generic (16-bit io);
+                        * 6 f32_tile64, 7 f32_tile32, 8 f32_splitk (fp32 io) */
+    int ks, mt;        /* template arguments of the instantiation; 0 where the family has none: k-steps held in registers, row tiles */
+    int wt, wvec, res, pf, wimg, pt, x3;   /* pt: pixels per workgroup (wg: the PT argument) */
+    int per, nz;       /* 32-row tiles per workgroup; wg: row-tile groups = grid_z */
+    int grid_x, grid_y, grid_z, block;
+    size_t lds_bytes;  /* dynamic LDS per workgroup */
+} oss_conv1x1_launch;
+int oss_conv1x1_describe(int input_gradient, oss_dtype io, const void *x, const float *weight, const void *image, const float *bias,
+                         const void *residual, const void *y, int batch, int cout, int cin, int pixels, int64_t x_batch_stride,
+                         int64_t x_channel_stride, oss_conv1x1_launch *out);
 void oss_conv1x1_wgrad_set_tile(int mode);
 /* pixels per partial product of the GROUPED weight-gradient launch (oss_flush_wgrads), in units of 512: the library starts at 4;
  * 1 reproduces the one-problem launches bit for bit, larger values write fewer partial vectors */
@@ -1068,12 +1085,13 @@ int oss_f32_matmul_modes(void);
  * oss_conv1x1_pack_* and the *_packed entry points; 10: oss_chan_params lost zt and dts, the channel kernels evaluate the
  * projections from the pooled vector; 11: the added entry point oss_proj_set_one_launch; 12: the added
  * entry points oss_jpeg_workgroups and oss_jpeg_roundtrip; 13: the added entry points oss_noise_workgroups,
- * oss_noise_scratch_words, oss_noise_gaussian, oss_noise_poisson, their *_host twins and oss_noise_normals_host); oss_abi_struct_bytes(which) is the library's own sizeof
+ * oss_noise_scratch_words, oss_noise_gaussian, oss_noise_poisson, their *_host twins and oss_noise_normals_host; 14: the added entry point
+ * oss_conv1x1_describe with its struct oss_conv1x1_launch); oss_abi_struct_bytes(which) is the library's own sizeof
  * (which: 0 = oss_scan_fwd_params, 1 = oss_scan_bwd_params, 2 = oss_chan_params; 0 for anything else).  Every binding layer
  * in this tree compares both with its own values when it loads and refuses to run on a mismatch: csrc_host/oss_torch_host.cpp
  * (through vmambair_amd/_host.py) with its compile-time ones, vmambair_amd/_capi.py with what it reads from this file -- the
  * number below is the only place to bump. */
-#define OSS_ABI_VERSION 13
+#define OSS_ABI_VERSION 14
 int oss_abi_version(void);
 size_t oss_abi_struct_bytes(int which);
 

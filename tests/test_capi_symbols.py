@@ -55,10 +55,10 @@ def test_prototypes_are_complete():
 
 
 def test_struct_layout_matches_header():
-    """Compile a C probe against the header that prints sizeof and every field's offsetof of all six structs, generated from
+    """Compile a C probe against the header that prints sizeof and every field's offsetof of all seven structs, generated from
     the parsed field lists, and compare with the ctypes classes."""
     structs = _cheader.read(HEADER).structs
-    assert list(structs) == ["oss_scan_fwd_params", "oss_scan_bwd_params", "oss_scan_launch", "oss_chan_params", "oss_sum_chunk", "oss_adam_chunk"]
+    assert list(structs) == ["oss_scan_fwd_params", "oss_scan_bwd_params", "oss_scan_launch", "oss_conv1x1_launch", "oss_chan_params", "oss_sum_chunk", "oss_adam_chunk"]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "vmambair_oss.h"', 'int main(void) {']
     want = []
     for name, cls in structs.items():

@@ -490,6 +490,30 @@ int oss_conv1x1_dgrad_packed(oss_dtype io, const void *dy, const float *weight, 
                    dgrad_image);
 }
 
+// the plan oss_conv1x1_fwd_packed / oss_conv1x1_dgrad_packed would run (oss_conv1x1_plan.h), after those entry points' own checks
+int oss_conv1x1_describe(int input_gradient, oss_dtype io, const void *x, const float *weight, const void *image, const float *bias,
+                         const void *residual, const void *y, int batch, int cout, int cin, int pixels, int64_t xsb, int64_t xsc,
+                         oss_conv1x1_launch *out) {
+    if (!out) return OSS_ERR_NULL;
+    *out = oss_conv1x1_launch{};
+    out->family = -1;
+    const int x3 = take_f32_split(io);
+    if (!io_ok<IO_16>(io)) image = nullptr;
+    if (!x || !weight || !y) return OSS_ERR_NULL;
+    if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0 || batch > 65535 || (!input_gradient && cout > 32 * 65535)) return OSS_ERR_SHAPE;
+    if (reinterpret_cast<uintptr_t>(image) & 15u) return OSS_ERR_SHAPE;
+    const Conv1x1Call c = input_gradient ? conv1x1_call(io, x, weight, nullptr, y, batch, cin, cout, pixels, xsb, xsc, 1, cin, nullptr, x3, image)
+                                         : conv1x1_call(io, x, weight, bias, y, batch, cout, cin, pixels, xsb, xsc, cin, 1, residual, x3, image);
+    Conv1x1Plan pl;
+    if (const int rc = conv1x1_plan(c, pl)) return rc;
+    out->family = pl.family;
+    out->ks = pl.ks; out->mt = pl.mt; out->wt = pl.wt; out->wvec = pl.wvec; out->res = pl.res; out->pf = pl.pf; out->wimg = pl.wimg;
+    out->pt = pl.pt; out->x3 = pl.x3; out->per = pl.per; out->nz = pl.nz;
+    out->grid_x = (int)pl.grid[0]; out->grid_y = (int)pl.grid[1]; out->grid_z = (int)pl.grid[2]; out->block = pl.block;
+    out->lds_bytes = pl.lds_bytes;
+    return OSS_OK;
+}
+
 size_t oss_conv1x1_wgrad_partial_floats(int batch, int cout, int cin, int pixels) {
     if (batch <= 0 || cout <= 0 || cin <= 0 || pixels <= 0) return 0;
     return (size_t)batch * conv1x1_wgrad_slabs(pixels) * cout * (cin + 1);  // + 1: the dbias column
@@ -550,8 +574,7 @@ int oss_conv1x1_wg(oss_dtype io, const void *x, const float *weight, const float
 }
 
 int oss_ln_conv1x1_ok(oss_dtype io, int cout, int cin, int pixels) {
-    const void *a = reinterpret_cast<const void *>(uintptr_t(256));   // shape / dtype rules only: an aligned stand-in for the pointers
-    return conv1x1_wg_ok(io, cout, cin, pixels, (int64_t)cin * pixels, pixels, a, a, reinterpret_cast<const float *>(a), nullptr);
+    return conv1x1_wg_takes(io, cout, cin, pixels, (int64_t)cin * pixels, pixels, 0, false) ? 1 : 0;   // shape / dtype rules only: aligned tensors
 }
 
 int oss_ln_conv1x1_fwd(oss_dtype io, const void *x, const float *ln_weight, const float *ln_bias, float eps, void *n, float *mean,

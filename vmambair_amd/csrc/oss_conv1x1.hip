@@ -853,127 +853,117 @@ oss_conv1x1_wgrad_finish(const float *__restrict__ part, float *__restrict__ dw,
     }
 }
 
-// how many waves a launch of the whole-K kernels aims for (row tiles are dealt to more workgroups until it is reached):
-// 1024 / 2048 / 4096: 177.0 / 176.2 / 175.0 images/s (profiles/r02_conv1x1_pipeline.txt)
-constexpr long kConv1x1TargetWaves = 1024;
-
+// The launchers run a plan (oss_conv1x1_plan.h: what to launch is decided there, once per call) and nothing else.
 // wimg: the pre-packed image of W for THIS direction (conv1x1_pack_fill), or NULL.  It only changes where the pixel-pair kernels
 // (and the workgroup-level ones of oss_conv1x1_wg.hip) fetch their weight fragments; the shapes those kernels do not take read
 // the fp32 weights as before.
 template <typename T>
-static void conv1x1_launch(const T *x, const float *w, const float *bias, T *y, int B, int M, int K, int P, int64_t xsb,
-                           int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const T *res, const void *wimg = nullptr) {
-    const int pblocks = (P + 127) / 128, mt = (M + 31) / 32;
-    const bool wt = (ws_m == 1 && ws_k == M);          // input gradient: weights read transposed
-    const bool plain = (ws_k == 1 && ws_m == K);
-    // pixel-pair form: even P, even row strides, 4-byte aligned bases
-    const bool pair_ok = P % 2 == 0 && xsk % 2 == 0 && xsb % 2 == 0 && xsk < (1 << 24) && (size_t)M * K < (1u << 30) &&
-                         (wt || plain) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 3u) == 0;
-    if (pair_ok) {
-        const bool wvec = plain && K % 8 == 0 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0;
-        const int pb = (P + 255) / 256;
-        const long waves_p = (long)B * ((P + 63) / 64);
-        const int xk = (int)xsk;
-        const u32x4 *img = reinterpret_cast<const u32x4 *>(wimg);
-        if (!img && plain && !wvec && K > 16 * 3 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0) {
-            // forward with rows that are not 16-byte aligned (K = 127, the EFFN hidden width at dim 48): weight tile through LDS
-            hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
-            return;
-        }
-        if (K <= 16 * 12) {
-            // whole K in registers: enough workgroups to fill the chip twice, otherwise as few activation re-loads as possible
-            int split = (int)((kConv1x1TargetWaves + waves_p - 1) / waves_p);
-            if (split < 1) split = 1;
-            if (split > mt) split = mt;
-            const int per = (mt + split - 1) / split;
-            dim3 grid(pb, B, (mt + per - 1) / per);
-#define OSS_PAIR2(KS_, WT_, WV_, PF_) do { if (res) hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, WT_, WV_, true, PF_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res); \
-                                           else     hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, WT_, WV_, false, PF_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res); } while (0)
-#define OSS_PAIR(KS_, PF_) do { if (wt) OSS_PAIR2(KS_, true, false, PF_); else if (wvec) OSS_PAIR2(KS_, false, true, PF_); else OSS_PAIR2(KS_, false, false, PF_); } while (0)
-#define OSS_PAIRI(KS_, PF_) do { if (res) hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, false, false, true, PF_, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res, img); \
-                                 else     hipLaunchKernelGGL((oss_conv1x1_pair_kernel<T, KS_, false, false, false, PF_, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res, img); } while (0)
-            // PF (next tile's operands in flight during the current tile): the raw fp32 fragments of two tiles fit up to 6 k-steps,
-            // the 16-bit fragments of an image up to 8
-            if (img) {
-                if (K <= 16 * 3)      OSS_PAIRI(3, true);
-                else if (K <= 16 * 6) OSS_PAIRI(6, true);
-                else if (K <= 16 * 8) OSS_PAIRI(8, true);
-                else                  OSS_PAIRI(12, false);
-            }
-            else if (K <= 16 * 3) OSS_PAIR(3, true);
-            else if (K <= 16 * 6) OSS_PAIR(6, true);
-            else if (K <= 16 * 8) OSS_PAIR(8, false);    // K = 127 (EFFN hidden width at dim 48): no duplicate k-steps
-            else                  OSS_PAIR(12, false);
-#undef OSS_PAIRI
-#undef OSS_PAIR2
-#undef OSS_PAIR
-        } else {
-            // K in chunks of 128: up to 3 row tiles accumulate per workgroup (fewest re-loads that still fill the chip)
-            int per = 3;
-            while (per > 1 && waves_p * ((mt + per - 1) / per) < 4096) --per;
-            if (per > mt) per = mt;
-            if (!img && per == 1 && K <= 512 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0 && plain) {   // forward: weights through LDS
-                hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, dim3(pb, B, mt), dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res);
-                return;
-            }
-            dim3 grid(pb, B, (mt + per - 1) / per);
-#define OSS_PAIR1(MT_, WT_, WV_) hipLaunchKernelGGL((oss_conv1x1_pairk_kernel<T, 8, MT_, WT_, WV_>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res)
-#define OSS_PAIR(MT_) do { if (wt) OSS_PAIR1(MT_, true, false); else if (wvec) OSS_PAIR1(MT_, false, true); else OSS_PAIR1(MT_, false, false); } while (0)
-#define OSS_PAIRI(MT_) hipLaunchKernelGGL((oss_conv1x1_pairk_kernel<T, 8, MT_, false, false, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, res, img)
-            if (img) { if (per == 1) OSS_PAIRI(1); else if (per == 2) OSS_PAIRI(2); else OSS_PAIRI(3); }
-            else if (per == 1) OSS_PAIR(1); else if (per == 2) OSS_PAIR(2); else OSS_PAIR(3);
-#undef OSS_PAIRI
-#undef OSS_PAIR
-#undef OSS_PAIR1
-        }
-        return;
-    }
-    const bool reuse_ok = K <= 16 * 12 && xsk < (1 << 24) && (size_t)M * K < (1u << 30) &&
-                          (wt || (plain && K % 8 == 0 && (reinterpret_cast<uintptr_t>(w) & 15u) == 0));
-    if (reuse_ok) {
-        // enough waves to fill 256 CUs x 4 SIMDs twice, otherwise as few activation re-loads as possible
-        const long waves_p = (long)B * ((P + 31) / 32);
-        int split = (int)((2048 + waves_p - 1) / waves_p);
-        if (split < 1) split = 1;
-        if (split > mt) split = mt;
-        const int per = (mt + split - 1) / split;
-        dim3 grid(pblocks, B, (mt + per - 1) / per);
-        const int xk = (int)xsk;
-        if (K <= 16 * 6) {
-            if (wt) hipLaunchKernelGGL((oss_conv1x1_reuse_kernel<T, 6, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res);
-            else    hipLaunchKernelGGL((oss_conv1x1_reuse_kernel<T, 6, false>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res);
-        } else {
-            if (wt) hipLaunchKernelGGL((oss_conv1x1_reuse_kernel<T, 12, true>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res);
-            else    hipLaunchKernelGGL((oss_conv1x1_reuse_kernel<T, 12, false>), grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xk, per, res);
-        }
-    } else {
-        dim3 grid(pblocks, B, mt);
-        hipLaunchKernelGGL(oss_conv1x1_kernel<T>, grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xsk, ws_m, ws_k, res);
-    }
+struct WaveArgs {
+    const T *x;
+    const float *w, *bias;
+    T *y;
+    int M, K, P;
+    int64_t xsb;
+    int xsk;
+    const T *res;
+    const u32x4 *img;
+    dim3 grid;
+    hipStream_t s;
+};
+// (WT, WVEC, WIMG) of the pixel-pair kernels: weights read transposed | as 16-byte rows | per element | from the image
+template <typename T, int KS, bool WT, bool WVEC, bool WIMG>
+static void pair_launch(const Conv1x1Plan &pl, const WaveArgs<T> &a) {
+    constexpr bool PF = conv1x1_pair_pf(KS, WIMG);
+    auto kern = pl.res ? oss_conv1x1_pair_kernel<T, KS, WT, WVEC, true, PF, WIMG> : oss_conv1x1_pair_kernel<T, KS, WT, WVEC, false, PF, WIMG>;
+    hipLaunchKernelGGL(kern, a.grid, dim3(256), 0, a.s, a.x, a.w, a.bias, a.y, a.M, a.K, a.P, a.xsb, a.xsk, pl.per, a.res, a.img);
 }
+template <typename T, int MT, bool WT, bool WVEC, bool WIMG>
+static void pairk_launch(const Conv1x1Plan &, const WaveArgs<T> &a) {
+    hipLaunchKernelGGL((oss_conv1x1_pairk_kernel<T, 8, MT, WT, WVEC, WIMG>), a.grid, dim3(256), 0, a.s, a.x, a.w, a.bias, a.y, a.M, a.K, a.P,
+                       a.xsb, a.xsk, a.res, a.img);
+}
+// OSS_PAIR_FORM(launcher, N): the plan's weight form of `launcher<T, N, WT, WVEC, WIMG>`
+#define OSS_PAIR_FORM(LAUNCH_, N_)                                      \
+    do {                                                                \
+        if (pl.wimg)      LAUNCH_<T, N_, false, false, true>(pl, a);    \
+        else if (pl.wt)   LAUNCH_<T, N_, true, false, false>(pl, a);    \
+        else if (pl.wvec) LAUNCH_<T, N_, false, true, false>(pl, a);    \
+        else              LAUNCH_<T, N_, false, false, false>(pl, a);   \
+    } while (0)
 
-// 0 = never the workgroup-level kernel of oss_conv1x1_wg.hip (A-B timing: conv1x1_set_wg)
-static std::atomic<int> g_conv_wg{1};
+template <typename T>
+static int conv1x1_launch(const Conv1x1Plan &pl, const T *x, const float *w, const float *bias, T *y, int M, int K, int P, int64_t xsb,
+                          int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const T *res, const void *wimg) {
+    const WaveArgs<T> a{x, w, bias, y, M, K, P, xsb, (int)xsk, res, reinterpret_cast<const u32x4 *>(wimg), dim3(pl.grid[0], pl.grid[1], pl.grid[2]), s};
+    switch (pl.family) {
+        case CONV1X1_PAIR:
+            switch (pl.ks) {
+                case 3: OSS_PAIR_FORM(pair_launch, 3); break;
+                case 6: OSS_PAIR_FORM(pair_launch, 6); break;
+                case 8: OSS_PAIR_FORM(pair_launch, 8); break;
+                case 12: OSS_PAIR_FORM(pair_launch, 12); break;
+                default: return OSS_ERR_SHAPE;
+            }
+            break;
+        case CONV1X1_PAIRK:
+            switch (pl.mt) {
+                case 1: OSS_PAIR_FORM(pairk_launch, 1); break;
+                case 2: OSS_PAIR_FORM(pairk_launch, 2); break;
+                case 3: OSS_PAIR_FORM(pairk_launch, 3); break;
+                default: return OSS_ERR_SHAPE;
+            }
+            break;
+        case CONV1X1_PAIRW:   // forward with rows that are not 16-byte aligned, or one row tile per workgroup: weight tile through LDS
+            hipLaunchKernelGGL(oss_conv1x1_pairw_kernel<T>, a.grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, a.xsk, res);
+            break;
+        case CONV1X1_REUSE: {
+            auto kern = pl.ks == 6 ? (pl.wt ? oss_conv1x1_reuse_kernel<T, 6, true> : oss_conv1x1_reuse_kernel<T, 6, false>)
+                                   : (pl.wt ? oss_conv1x1_reuse_kernel<T, 12, true> : oss_conv1x1_reuse_kernel<T, 12, false>);
+            hipLaunchKernelGGL(kern, a.grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, a.xsk, pl.per, res);
+            break;
+        }
+        case CONV1X1_GENERIC:
+            hipLaunchKernelGGL(oss_conv1x1_kernel<T>, a.grid, dim3(256), 0, s, x, w, bias, y, M, K, P, xsb, xsk, ws_m, ws_k, res);
+            break;
+        default: return OSS_ERR_SHAPE;
+    }
+    return (int)hipGetLastError();
+}
+#undef OSS_PAIR_FORM
+
+// test-only overrides (oss_conv1x1_set_wg), handed to the plan as values: 0 = never the workgroup-level kernel of
+// oss_conv1x1_wg.hip (A-B timing); pixels per workgroup of that kernel, 64 | 128, 0 = by shape
+static std::atomic<int> g_conv_wg{1}, g_wg_pixels{0};
 
 void conv1x1_set_wg(int on) { g_conv_wg.store(on ? 1 : 0); }
+void conv1x1_wg_set_pixels(int pt) { g_wg_pixels.store(pt == 64 || pt == 128 ? pt : 0); }
+
+Conv1x1Call conv1x1_call(oss_dtype io, const void *x, const float *w, const float *bias, const void *y, int B, int M, int K, int P,
+                         int64_t xsb, int64_t xsk, int64_t ws_m, int64_t ws_k, const void *res, int f32_split, const void *wimg) {
+    const auto lo = [](const void *p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u); };
+    Conv1x1Call c{};
+    c.io = io; c.B = B; c.M = M; c.K = K; c.P = P;
+    c.xsb = xsb; c.xsk = xsk; c.ws_m = ws_m; c.ws_k = ws_k;
+    c.x_lo = lo(x); c.y_lo = lo(y); c.w_lo = lo(w); c.res_lo = lo(res); c.wimg_lo = lo(wimg);
+    c.has_bias = bias != nullptr; c.has_res = res != nullptr; c.has_wimg = wimg != nullptr;
+    c.f32_split = f32_split != 0;
+    c.wg_on = g_conv_wg.load(); c.wg_pixels = g_wg_pixels.load();
+    return c;
+}
 
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
             int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res, int f32_split, const void *wimg) {
-    {
-        const bool wt = (ws_m == 1 && ws_k == M), plain = (ws_k == 1 && ws_m == K);
-        if ((wt || plain) && g_conv_wg.load() != 0 && conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res))
-            return conv1x1_wg(io, x, w, bias, y, B, M, K, P, xsb, xsk, wt ? 1 : 0, s, res, wimg);
-    }
+    Conv1x1Plan pl;
+    if (const int rc = conv1x1_plan(conv1x1_call(io, x, w, bias, y, B, M, K, P, xsb, xsk, ws_m, ws_k, res, f32_split, wimg), pl)) return rc;
+    if (pl.family == CONV1X1_WG) return conv1x1_wg_run(pl, io, x, w, bias, y, M, P, xsb, xsk, s, wimg);
     return io_dispatch(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
         const T *xp = reinterpret_cast<const T *>(x), *rp = reinterpret_cast<const T *>(res);
         T *yp = reinterpret_cast<T *>(y);
-        if constexpr (sizeof(T) == 4) {   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
-            return conv1x1_f32(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, f32_split);
-        } else {
-            conv1x1_launch<T>(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, wimg);
-            return (int)hipGetLastError();
-        }
+        if constexpr (sizeof(T) == 4)   // fp32 I/O: true fp32 on the matrix cores (oss_conv1x1_f32.hip), no reduced-precision detour
+            return conv1x1_f32(xp, w, bias, yp, B, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, pl);
+        else
+            return conv1x1_launch<T>(pl, xp, w, bias, yp, M, K, P, xsb, xsk, ws_m, ws_k, s, rp, wimg);
     });
 }
 

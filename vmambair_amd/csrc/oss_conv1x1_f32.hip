@@ -228,41 +228,40 @@ static bool f32_aligned(std::initializer_list<const void *> ptrs, std::initializ
     return true;
 }
 
-// split != 0: fp32 tensors, products on split bf16 (OSS_F32_BF16X3) -- same shape rules, same tiles per launch form
-int gemm_f32(const F32Gemm &a, int B, hipStream_t s, int split) {
-    if (a.M < 1 || a.K < 1 || a.P < 4 || a.P % 4 != 0 || a.G < 1 || a.GX < 1) return OSS_ERR_SHAPE;
-    if (!f32_aligned({a.x, a.y, a.res}, {a.xsb, a.xsg, a.xsk, a.ysb, a.ysg, a.ysm, a.rsb, a.rsg, a.rsm})) return OSS_ERR_SHAPE;
-    if (B <= 0 || (long)B * a.G > 65535) return OSS_ERR_SHAPE;
-    const bool x3 = split && kF32SplitGemm;
-    const long px = (a.P + 127) / 128, bg = (long)B * a.G;
-    const long waves64 = px * ((a.M + 63) / 64) * bg, waves32 = px * ((a.M + 31) / 32) * bg;
-    if (waves64 >= 3072 && a.M > 32) {          // plenty of tiles: 64-row tiles, one wave each
-        const dim3 grid(px, (a.M + 63) / 64, bg);
-        if (x3) hipLaunchKernelGGL((oss_conv1x1_f32_kernel<2, false, true>), grid, dim3(64), 0, s, a);
-        else    hipLaunchKernelGGL((oss_conv1x1_f32_kernel<2, false>), grid, dim3(64), 0, s, a);
-    } else if (waves32 >= 3072 || a.K < (x3 ? 64 : 32)) {   // 32-row tiles, one wave each (a short K has nothing to split: x3 works in rounds of 16)
-        const dim3 grid(px, (a.M + 31) / 32, bg);
-        if (x3) hipLaunchKernelGGL((oss_conv1x1_f32_kernel<1, false, true>), grid, dim3(64), 0, s, a);
-        else    hipLaunchKernelGGL((oss_conv1x1_f32_kernel<1, false>), grid, dim3(64), 0, s, a);
-    } else {                                    // few tiles: four waves per tile, a quarter of K each
-        const dim3 grid(px, (a.M + 31) / 32, bg);
-        static LdsGate gate;
-        const size_t smem = sizeof(float) * 3 * 16 * 64 * 4;
-        auto kern = x3 ? oss_conv1x1_f32_kernel<1, true, true> : oss_conv1x1_f32_kernel<1, true>;
-        if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
+// launches an fp32 plan (oss_conv1x1_plan.h: conv1x1_f32_plan picks the tile form; X3 = the products on split bf16, OSS_F32_BF16X3)
+static int gemm_f32_launch(const F32Gemm &a, const Conv1x1Plan &pl, hipStream_t s) {
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+    void (*kern)(const F32Gemm) = nullptr;
+    switch (pl.family) {
+        case CONV1X1_F32_TILE64: kern = pl.x3 ? oss_conv1x1_f32_kernel<2, false, true> : oss_conv1x1_f32_kernel<2, false>; break;
+        case CONV1X1_F32_TILE32: kern = pl.x3 ? oss_conv1x1_f32_kernel<1, false, true> : oss_conv1x1_f32_kernel<1, false>; break;
+        case CONV1X1_F32_SPLITK: kern = pl.x3 ? oss_conv1x1_f32_kernel<1, true, true> : oss_conv1x1_f32_kernel<1, true>; break;
+        default: return OSS_ERR_SHAPE;
     }
+    static LdsGate gate;   // of the split-K form, the only one with dynamic LDS
+    if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), pl.lds_bytes)) return e;
+    hipLaunchKernelGGL(kern, grid, dim3(pl.block), pl.lds_bytes, s, a);
     return (int)hipGetLastError();
 }
 
+// the products of B batches x a.G groups; split != 0: fp32 tensors, products on split bf16 -- same shape rules, same tiles per form
+int gemm_f32(const F32Gemm &a, int B, hipStream_t s, int split) {
+    if (a.G < 1 || a.GX < 1) return OSS_ERR_SHAPE;
+    const bool aligned = f32_aligned({a.x, a.y, a.res}, {a.xsb, a.xsg, a.xsk, a.ysb, a.ysg, a.ysm, a.rsb, a.rsg, a.rsm});
+    Conv1x1Plan pl;
+    if (const int rc = conv1x1_f32_plan(a.M, a.K, a.P, (long)B * a.G, aligned, split != 0, pl)) return rc;
+    return gemm_f32_launch(a, pl, s);
+}
+
 int conv1x1_f32(const float *x, const float *w, const float *bias, float *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, int split) {
+                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, const Conv1x1Plan &pl) {
+    (void)B;   // in the plan's grid
     F32Gemm a{};
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.y = y;
     a.M = M; a.K = K; a.P = P; a.G = 1; a.GX = 1; a.accumulate = 0;
     a.xsb = xsb; a.xsg = 0; a.xsk = xsk; a.wsg = 0; a.wsm = wsm; a.wsk = wsk;
     a.ysb = (int64_t)M * P; a.ysg = 0; a.ysm = P; a.rsb = a.ysb; a.rsg = 0; a.rsm = P;
-    return gemm_f32(a, B, s, split);
+    return gemm_f32_launch(a, pl, s);
 }
 
 // x_proj / dt_proj of the four scan directions at fp32 I/O (MambaSISR6_arch.py:406-411) -- the products oss_proj_fwd / oss_proj_dgrad

@@ -23,7 +23,8 @@ namespace oss {
 
 // The weight-gradient family and the forward / input-gradient family are switched separately: a family that is not faster on split
 // bf16 would stay on the exact kernel under "high" too.  Both are (profiles/fp32_matmul_high_ab.txt).
-constexpr bool kF32SplitGemm = true, kF32SplitWgrad = true;
+// (kF32SplitGemm, the forward / input-gradient family's switch, is a launch decision: oss_conv1x1_plan.h)
+constexpr bool kF32SplitWgrad = true;
 
 // Two values -> packed hi and lo.  The finite case costs five instructions per pair (cvt_pk, shift, and, packed subtract, cvt_pk);
 // `bad` turns NaN when a remainder is not finite (r * 0 is NaN exactly then) and the caller then repairs its round (below).

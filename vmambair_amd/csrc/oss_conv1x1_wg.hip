@@ -13,8 +13,6 @@
 //      [pixel][8 channels] fragment the MFMA wants comes out of a [channel][pixel] image without any strided access,
 //   3. gives every wave whole 32-row tiles of the output over all 128 pixels (four MFMA column tiles per weight fragment),
 //   4. sends the results through a wave-private LDS tile and out as 16-byte stores along the pixel axis.
-#include <algorithm>
-#include <atomic>
 #include <type_traits>
 #include "oss_device.h"
 #include "oss_host.h"
@@ -309,65 +307,37 @@ oss_conv1x1_wg_kernel(const T *__restrict__ x, const float *__restrict__ w, cons
     }
 }
 
-constexpr int kWgXPad = 32;
-// (the staging tile is sized for its widest pitch, PT + 16)
-static size_t wg_lds_bytes(int K, int pt, bool res) { return (size_t)K * 2 * (pt + kWgXPad) + (size_t)4 * 32 * (res ? 4 : 2) * (pt + 16) + 2 * (size_t)K * sizeof(float); }   // + the LayerNorm weight / bias image
-// pixels per workgroup (64 | 128) and the row-tile split (gridDim.z): 0 = by shape, else forced (A-B timing).  Measured
-// (tools/conv_wg_test.py, and inside the SR and Deraining steps): K = 96 / 192 want 128 pixels when that still gives a
-// workgroup per CU, K <= 48 wants 64; a launch with fewer workgroups than CUs (Deraining levels 1.. at batch 4) loses to the
-// wave-level kernels unless its row tiles are split over more workgroups.
-static std::atomic<int> g_wg_pixels{0};
-void conv1x1_wg_set_pixels(int pt) { g_wg_pixels.store(pt == 64 || pt == 128 ? pt : 0); }
-static void wg_shape(int B, int M, int K, int P, int &pt, int &nz) {
-    const int f = g_wg_pixels.load();
-    const long t128 = (long)B * (P / 128);
-    pt = f ? f : ((K <= 48 && t128 < 1024) || t128 < 256 ? 64 : 128);
-    const long wgs = (long)B * (P / pt);
-    const int groups = ((M + 31) / 32 + 3) / 4;           // row tiles in units of a workgroup's four waves
-    nz = (int)std::min<long>(groups, (256 + wgs - 1) / wgs);   // a workgroup per CU
-    if (nz < 1) nz = 1;
-}
-
-static constexpr bool wg_ks_built(int ks) { return ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 6 || ks == 8 || ks == 12; }
-// 1 when the workgroup-level kernel takes the shape
+// 1 when the workgroup-level kernel takes the shape (oss_conv1x1_plan.h: conv1x1_wg_takes)
 int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, const void *x, const void *y, const float *w,
                   const void *res) {
-    // The fused skip connection (RES) is written and parity-green, but inside the training step it measured SLOWER than the
-    // wave-level kernel (10.6 vs 9.4 us at 96 -> 96: the residual arrives cold from HBM behind the fp32 LDS round trip), so
-    // those calls stay where they were and the RES instantiations are not built.
-    if (res) return 0;
-    if (!io_ok<IO_16>(io)) return 0;
-    if (K % 16 != 0 || K < 16 || K > 192 || P % 128 != 0 || M < 1) return 0;
-    // built for the widths a power-of-two-times-{1,3} base width gives (K = 16, 32, 48, 64, 96, 128, 192: dim 16 / 32 / 48 / 64 and
-    // their doublings); K = 80, 112, 144, 160, 176 stay on the wave-level kernels (round 5: 80 instantiations nobody launched)
-    if (!wg_ks_built(K / 16)) return 0;
-    if (xsb % 8 != 0 || xsk % 8 != 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(res)) & 15u)
-        return 0;
-    return wg_lds_bytes(K, 128, res != nullptr) <= kMaxLdsBytes ? 1 : 0;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(res);
+    return conv1x1_wg_takes(io, M, K, P, xsb, xsk, (unsigned)(lo & 15u), res != nullptr) ? 1 : 0;
 }
 
-template <typename T, bool WT, bool LN = false>
-static int wg_launch(const T *x, const float *w, const float *bias, T *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                     const T *res, hipStream_t s, WgLnArgs<T> ln = WgLnArgs<T>{}, const void *wimg = nullptr) {
-    int pt, nz;
-    wg_shape(B, M, K, P, pt, nz);
-    const size_t smem = wg_lds_bytes(K, pt, res != nullptr);
-    dim3 grid(P / pt, B, nz);
+// launches a CONV1X1_WG plan (the RES instantiations are not built: the plan never takes a call with a residual)
+template <typename T, bool LN>
+static int wg_launch(const Conv1x1Plan &pl, const T *x, const float *w, const float *bias, T *y, int M, int P, int64_t xsb, int64_t xsk,
+                     hipStream_t s, WgLnArgs<T> ln, const void *wimg) {
+    const size_t smem = pl.lds_bytes;
+    const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
     const u32x4 *img = reinterpret_cast<const u32x4 *>(wimg);
-#define OSS_WG3(KS_, PT_, RES_, IMG_)                                                                                \
+    const T *res = nullptr;
+#define OSS_WG3(KS_, WT_, PT_, IMG_)                                                                                 \
     do {                                                                                                             \
         static LdsGate gate;                                                                                         \
-        auto kern = oss_conv1x1_wg_kernel<T, KS_, WT, PT_, RES_, (KS_ <= 6), LN, IMG_>;                                  \
+        auto kern = oss_conv1x1_wg_kernel<T, KS_, WT_, PT_, false, conv1x1_wg_pf(KS_), LN, IMG_>;                    \
         if (const int e = gate.ensure(reinterpret_cast<const void *>(kern), smem)) return e;                         \
-        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, x, w, bias, y, M, P, xsb, xsk, res, ln, img);                 \
+        hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, x, w, bias, y, M, P, xsb, xsk, res, ln, img);             \
     } while (0)
-#define OSS_WG(KS_)                                                                                                  \
+#define OSS_WG2(KS_, WT_)                                                                                            \
     do {                                                                                                             \
-        if (img) { if (pt == 128) OSS_WG3(KS_, 128, false, true); else OSS_WG3(KS_, 64, false, true); }              \
-        else     { if (pt == 128) OSS_WG3(KS_, 128, false, false); else OSS_WG3(KS_, 64, false, false); }            \
+        if (pl.wimg) { if (pl.pt == 128) OSS_WG3(KS_, WT_, 128, true); else OSS_WG3(KS_, WT_, 64, true); }           \
+        else         { if (pl.pt == 128) OSS_WG3(KS_, WT_, 128, false); else OSS_WG3(KS_, WT_, 64, false); }         \
     } while (0)
-    switch (K / 16) {
+    // (the LayerNorm form is a forward: WT = true is not built for it, `!LN` names WT = false there)
+#define OSS_WG(KS_) do { if (!LN && pl.wt) OSS_WG2(KS_, !LN); else OSS_WG2(KS_, false); } while (0)
+    if (pl.family != CONV1X1_WG || (LN && pl.wt)) return OSS_ERR_SHAPE;
+    switch (pl.ks) {
         case 1: OSS_WG(1); break;
         case 2: OSS_WG(2); break;
         case 3: OSS_WG(3); break;
@@ -378,21 +348,29 @@ static int wg_launch(const T *x, const float *w, const float *bias, T *y, int B,
         default: return OSS_ERR_SHAPE;
     }
 #undef OSS_WG
+#undef OSS_WG2
 #undef OSS_WG3
     return (int)hipGetLastError();
 }
 
-// wt = 0: y = W x + bias [+ res] with w (M, K) row-major; wt = 1: W(m, k) = w[k * M + m] (the input gradient of a (K, M) weight)
-int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
-               int64_t xsk, int wt, hipStream_t s, const void *res, const void *wimg) {
-    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, res) || (reinterpret_cast<uintptr_t>(wimg) & 15u)) return OSS_ERR_SHAPE;
+int conv1x1_wg_run(const Conv1x1Plan &pl, oss_dtype io, const void *x, const float *w, const float *bias, void *y, int M, int P,
+                   int64_t xsb, int64_t xsk, hipStream_t s, const void *wimg) {
     return io_dispatch<IO_16>(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
-        const T *xp = reinterpret_cast<const T *>(x), *rp = reinterpret_cast<const T *>(res);
-        T *yp = reinterpret_cast<T *>(y);
-        return wt ? wg_launch<T, true>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s, WgLnArgs<T>{}, wimg)
-                  : wg_launch<T, false>(xp, w, bias, yp, B, M, K, P, xsb, xsk, rp, s, WgLnArgs<T>{}, wimg);
+        return wg_launch<T, false>(pl, reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), M, P, xsb, xsk, s, WgLnArgs<T>{}, wimg);
     });
+}
+
+// wt = 0: y = W x + bias with w (M, K) row-major; wt = 1: W(m, k) = w[k * M + m] (the input gradient of a (K, M) weight).
+// The workgroup-level kernel or OSS_ERR_SHAPE, whatever oss_conv1x1_set_wg's `on` says.
+int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
+               int64_t xsk, int wt, hipStream_t s, const void *res, const void *wimg) {
+    Conv1x1Call c = conv1x1_call(io, x, w, bias, y, B, M, K, P, xsb, xsk, wt ? 1 : K, wt ? M : 1, res, 0, wimg);
+    c.wg_on = 1;
+    Conv1x1Plan pl;
+    if (const int rc = conv1x1_plan(c, pl)) return rc;
+    if (pl.family != CONV1X1_WG) return OSS_ERR_SHAPE;
+    return conv1x1_wg_run(pl, io, x, w, bias, y, M, P, xsb, xsk, s, wimg);
 }
 
 // ---- input gradient of a 1x1 convolution + the backward of the LayerNorm in front of it, one launch ---------------------------
@@ -617,18 +595,14 @@ oss_wg_lnbwd_finish(const float *__restrict__ part, float *__restrict__ dw, floa
 size_t conv1x1_dgrad_lnbwd_partial_floats(int B, int M, int P) { return (size_t)B * (P / 64) * 2 * M; }
 
 int conv1x1_dgrad_lnbwd_ok(oss_dtype io, int M, int K, int P, int B) {
-    if (!io_ok<IO_16>(io)) return 0;
-    if (K % 16 != 0 || K < 2 * M || K > 192 || M < 1 || M > 128 || P % 128 != 0) return 0;
-    const int ks = K / 16;
-    // (An any-K form for project_in after norm2 -- K = 2 hidden = 510, 64-pixel workgroups, weights fetched in chunks of 8 k-steps --
-    // was built, parity-green, and measured slower inside the step: 219.2 against 221.7 images/s with the two separate kernels.)
-    return (ks == 2 || ks == 3 || ks == 4 || ks == 6 || ks == 8 || ks == 12) ? 1 : 0;
+    (void)B;
+    return conv1x1_lnbwd_takes(io, M, K, P) ? 1 : 0;
 }
 
 template <typename T>
 static int lnbwd_launch(const T *dy, const float *w, int B, int M, int K, int P, int64_t xsb, int64_t xsk, WgLnBwdArgs<T> a, float *dlw,
                         float *dlb, hipStream_t s) {
-    const int pt = (long)B * (P / 128) >= 256 ? 128 : 64;
+    const int pt = conv1x1_lnbwd_pixels(B, P);
     const size_t smem = sizeof(uint16_t) * ((size_t)K + 4 * 32) * (pt + 8) + sizeof(float) * 2 * 8 * 128;
     dim3 grid(P / pt, B);
 #define OSS_LNB(KS_, PT_, BF_)                                                                              \
@@ -680,13 +654,15 @@ int conv1x1_dgrad_lnbwd(oss_dtype io, const void *dy, const float *w, const void
 int ln_conv1x1_wg(oss_dtype io, const void *x, const float *ln_w, const float *ln_b, float eps, void *n, float *mean, float *rstd,
                   const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk, hipStream_t s,
                   const void *wimg) {
-    if (!conv1x1_wg_ok(io, M, K, P, xsb, xsk, x, y, w, nullptr) || ((reinterpret_cast<uintptr_t>(n) | reinterpret_cast<uintptr_t>(wimg)) & 15u))
-        return OSS_ERR_SHAPE;
+    Conv1x1Call c = conv1x1_call(io, x, w, bias, y, B, M, K, P, xsb, xsk, K, 1, nullptr, 0, wimg);
+    c.ln = true;
+    c.y_lo |= (unsigned)(reinterpret_cast<uintptr_t>(n) & 15u);   // both outputs
+    Conv1x1Plan pl;
+    if (const int rc = conv1x1_plan(c, pl)) return rc;
     return io_dispatch<IO_16>(io, [&](auto tag) {
         using T = typename decltype(tag)::type;
         WgLnArgs<T> a{ln_w, ln_b, reinterpret_cast<T *>(n), mean, rstd, eps};
-        return wg_launch<T, false, true>(reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), B, M, K, P, xsb, xsk, nullptr, s, a,
-                                         wimg);
+        return wg_launch<T, true>(pl, reinterpret_cast<const T *>(x), w, bias, reinterpret_cast<T *>(y), M, P, xsb, xsk, s, a, wimg);
     });
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/vmambair_oss.h"
+#include "oss_conv1x1_plan.h"
 #include "oss_scan_plan.h"
 
 #include <atomic>
@@ -95,7 +96,7 @@ int dwconv3x3_wgrad(oss_dtype io, const void *x, const void *dy, float *dw, floa
                     void *dpre = nullptr);
 // fp32 I/O on v_mfma_f32_32x32x2_f32 (oss_conv1x1_f32.hip); split != 0: the products on split bf16 (OSS_F32_BF16X3, oss_conv1x1_f32x3.h)
 int conv1x1_f32(const float *x, const float *w, const float *bias, float *y, int B, int M, int K, int P, int64_t xsb, int64_t xsk,
-                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, int split = 0);
+                int64_t wsm, int64_t wsk, hipStream_t s, const float *res, const Conv1x1Plan &pl);
 int proj_f32_ok(int B, int D, int C, int R, int L, std::initializer_list<const void *> ptrs);
 int proj_fwd_f32(const float *x2, const float *Wx, const float *Wdt, float *xdbl, float *dts, int B, int D, int C, int R, int L,
                  hipStream_t s, int split = 0);
@@ -146,11 +147,16 @@ void conv1x1_set_wg(int on);
 void conv1x1_wg_set_pixels(int pt);
 int conv1x1_wg_ok(oss_dtype io, int M, int K, int P, int64_t xsb, int64_t xsk, const void *x, const void *y, const float *w,
                   const void *res = nullptr);
+int conv1x1_wg_run(const Conv1x1Plan &pl, oss_dtype io, const void *x, const float *w, const float *bias, void *y, int M, int P,
+                   int64_t xsb, int64_t xsk, hipStream_t s, const void *wimg);   // launches a CONV1X1_WG plan
 int conv1x1_wg(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
                int64_t xsk, int wt, hipStream_t s, const void *res = nullptr, const void *wimg = nullptr);
 int conv1x1(oss_dtype io, const void *x, const float *w, const float *bias, void *y, int B, int M, int K, int P, int64_t xsb,
             int64_t xsk, int64_t ws_m, int64_t ws_k, hipStream_t s, const void *res = nullptr, int f32_split = 0,
             const void *wimg = nullptr /* pre-packed 16-bit image of W for this direction (conv1x1_pack) */);
+// the call as the plan sees it (oss_conv1x1_plan.h): shapes, low address bits, null-ness and the two oss_conv1x1_set_wg overrides
+Conv1x1Call conv1x1_call(oss_dtype io, const void *x, const float *w, const float *bias, const void *y, int B, int M, int K, int P,
+                         int64_t xsb, int64_t xsk, int64_t ws_m, int64_t ws_k, const void *res, int f32_split, const void *wimg);
 // pre-packed weight images of the pixel-pair kernels (oss_conv1x1.hip)
 size_t conv1x1_image_bytes(int M, int K);
 size_t conv1x1_pack_row_bytes();
